@@ -11,9 +11,12 @@ HBM before the timed region; one step = zero_grad -> Net.forward (HIP interp, bi
 de-interp, HIP DEC) -> ae_mse + 10*kl -> backward -> RCCL gradient all-reduce -> clip 15 -> Adam(amsgrad)
 on a per-GPU batch of --batch encounters (weak scaling: the per-GPU batch is fixed as N grows).
 
-Besides the contract line it reports, for the dominant hand-written kernel, achieved algorithmic HBM GB/s
-(HIP-event timed on the launch stream) against the 8 TB/s peak, a per-kernel table, and the CPU oracle
-("port" of the reference path, oracle/dic_oracle.py) timed on this host's cores on a bounded sample.
+A plain run sets up, warms up, times --steps steps and prints the contract line (roofline / cpu_baseline null);
+--dump-outputs DIR then also writes what the last timed step computed (loss terms, gradient norm, latents, the
+parameters it left) as DIR/<name>.npy.  With --full the line also reports, for the dominant hand-written kernel,
+achieved algorithmic HBM GB/s (HIP-event timed on the launch stream) against the 8 TB/s peak, a per-kernel table,
+and the CPU oracle ("port" of the reference path, oracle/dic_oracle.py) timed on this host's cores on a bounded
+sample, and the secondary records (bench_secondary.json) follow it.
 """
 import argparse
 import json
@@ -30,6 +33,7 @@ import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0       # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.3 TB/s achievable)
 C, T, H, LAM, R, D = 6, 96, 24.0, 50.0, 24, 256
+DUMP_MAX_BYTES = 64 << 20       # --dump-outputs: all files together
 
 
 def parse():
@@ -59,6 +63,10 @@ def parse():
     p.add_argument('--scaling', choices=['weak', 'strong'], default=os.environ.get('DIC_BENCH_SCALING', 'weak'),
                    help='weak (default): --encounters resident and --batch per step PER GPU.  strong: ONE cohort of --encounters sharded over the '
                         'ranks and a fixed GLOBAL batch of --batch per step (BASELINE configs[2]: 75k encounters, K=8, on 8 GPUs)')
+    p.add_argument('--full', action='store_true', help='after the timed steps also measure the kernel table, the in-step trace (roofline), the CPU '
+                   'baseline and the secondary records; --no-cpu-baseline, --no-secondary, --no-sweep and --kernel-iters act only with it')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None, help='write what the last timed step computed (loss terms, gradient norm, '
+                   f'latents, the parameters it left) as DIR/<name>.npy, float32 / float64, at most {DUMP_MAX_BYTES >> 20} MB in all')
     return p.parse_args()
 
 
@@ -844,6 +852,29 @@ def log(*msg):
     print('[bench]', *msg, file=sys.stderr, flush=True)
 
 
+def dump_outputs(d, losses, gnorm, latents, net):
+    """--dump-outputs: what a caller of the timed step receives from its last call -- the loss terms, the gradient norm, the latents -- and the
+    parameters / buffers that step left, as d/<name>.npy (float32; float64 for the scalars and integer buffers).  The latents fill what the
+    DUMP_MAX_BYTES budget leaves; a larger batch keeps a fixed seeded sample of their rows (latents_rows.npy: the row indices)."""
+    os.makedirs(d, exist_ok=True)
+    arrs = {f'losses.{k}': np.asarray(float(v.detach()) if torch.is_tensor(v) else float(v), dtype=np.float64) for k, v in losses.items()}
+    arrs['grad_norm'] = np.asarray(float(gnorm), dtype=np.float64)
+    for k, v in net.state_dict().items():
+        v = v.detach().cpu()
+        arrs[f'params.{k}'] = v.numpy().astype(np.float32 if v.is_floating_point() else np.float64)
+    z = latents.detach().float().cpu().numpy()
+    room = DUMP_MAX_BYTES - sum(v.nbytes + 128 for v in arrs.values()) - 2 * 4096       # (npy headers; the row index file)
+    row_bytes = 4 * max(1, int(np.prod(z.shape[1:])))
+    if z.shape[0] * row_bytes > room:
+        rows = np.sort(np.random.default_rng(0).choice(z.shape[0], max(1, room // (row_bytes + 8)), replace=False))
+        z = z[rows]
+        arrs['latents_rows'] = rows.astype(np.float64)
+    arrs['latents'] = np.ascontiguousarray(z, dtype=np.float32)
+    for k, v in arrs.items():
+        np.save(os.path.join(d, k + '.npy'), v)
+    log(f'{len(arrs)} outputs of the last timed step -> {d} ({sum(v.nbytes for v in arrs.values()) / 2 ** 20:.1f} MB)')
+
+
 def csrc_sha16():
     """sha256 (first 16 hex digits) over the kernel sources, in name order: profiles/traffic.json / step_traffic.json record the value they were
     measured on (scripts/pmc_traffic.py, step_traffic.py), and a line printed from OTHER sources says traffic: null instead of repeating a
@@ -980,7 +1011,7 @@ def main():
     t0 = time.perf_counter()
     rows_stepped = 0
     for i in range(a.steps):
-        losses, gnorm, _ = one_step(a.warmup + i)
+        losses, gnorm, latents = one_step(a.warmup + i)
         rows_stepped += rows_of(a.warmup + i)[1] - rows_of(a.warmup + i)[0]
     barrier()
     el = time.perf_counter() - t0
@@ -990,10 +1021,31 @@ def main():
         el = float(tt)
     final_loss = float(losses['loss'].detach())
     log(f'{a.steps} steps = {rows_stepped} encounters per rank in {el:.3f}s ({1e3 * el / a.steps:.2f} ms/step), loss {final_loss:.5f}')
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, losses, gnorm, latents, net)        # (before anything else steps the net)
 
     if rank == 0:
         ms = 1e3 * el / a.steps
         value = world * rows_stepped / el          # encounters actually stepped (every rank walks the same batch sizes)
+        workload = ((f'{n_enc} of ONE {max(a.encounters, a.batch * world)}-encounter synthetic cohort per GPU' if strong else f'{n_enc} synthetic encounters/GPU') +
+                    f', 6 vitals, ~50 irregular samples per channel per 24h (T={T}), R={R}, K={K}, loss ' +
+                    ('ae_mse+fake_detect+10*kl' if a.fake_detection else 'ae_mse+10*kl') + ' [BASELINE.json configs[' + ('2' if K == 8 else '1') + ']]' +
+                    f'; every epoch walks the WHOLE cohort behind a fresh permutation: {nb} batches of {a.batch} incl. the last of {n_enc - (nb - 1) * a.batch} '
+                    f'(no drop_last, as upstream); value = encounters stepped / s; ms_per_step = mean over those steps')
+        out = {
+            'metric': 'encounters/sec per joint interp+DEC step', 'value': round(value, 1), 'unit': 'encounters/s',
+            'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(ms, 3),
+            'higher_is_better': True, 'scaling': a.scaling, 'vs_baseline': None, 'dtype': a.dtype, 'data': 'synthetic',
+            'config': {'workload': workload, 'per_gpu_batch': a.batch, 'global_batch': a.batch * world, 'batches_per_epoch': nb,
+                       'encounters_stepped': world * rows_stepped, 'parallelism': f'dp{world}' if world > 1 else 'single',
+                       'index_order': 'shuffled' if shuffled else 'file order',
+                       'input': 'padded (B,4C,T) batches' if store is None else f'ragged encounter store read in place ({store.nbytes() / 1e6:.0f} MB resident)'},
+            'roofline': None,
+            'cpu_baseline': None,
+        }
+    if rank == 0 and not a.full:
+        print(contract_line(out), flush=True)          # a plain run: the headline only (roofline and CPU baseline come with --full)
+    elif rank == 0:
         lo = 0
         table = kernel_table(net, X[lo:lo + a.batch], OB[lo:lo + a.batch], LEN[lo:lo + a.batch], K, a.kernel_iters)
         log('kernel table done:', {k: v['ms'] for k, v in table.items()})
@@ -1076,11 +1128,6 @@ def main():
                 log(f"roofline.traffic: null -- profiles/traffic.json was measured on other kernel sources ({tj.get('_csrc_sha16')} != {csrc_sha16()}): re-run scripts/profile_round.sh")
         custom_ms = sum(per_step.values())
         gflop = FLOP_PER_ENCOUNTER * (rows_stepped / a.steps) / 1e9          # (of an average step of the timed loop)
-        workload = ((f'{n_enc} of ONE {max(a.encounters, a.batch * world)}-encounter synthetic cohort per GPU' if strong else f'{n_enc} synthetic encounters/GPU') +
-                    f', 6 vitals, ~50 irregular samples per channel per 24h (T={T}), R={R}, K={K}, loss ' +
-                    ('ae_mse+fake_detect+10*kl' if a.fake_detection else 'ae_mse+10*kl') + ' [BASELINE.json configs[' + ('2' if K == 8 else '1') + ']]' +
-                    f'; every epoch walks the WHOLE cohort behind a fresh permutation: {nb} batches of {a.batch} incl. the last of {n_enc - (nb - 1) * a.batch} '
-                    f'(no drop_last, as upstream); value = encounters stepped / s; ms_per_step = mean over those steps')
         roofline = {'bound': 'hbm', 'kernel': dom, 'achieved': round(dom_gbps, 1), 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                     'frac': round(dom_gbps / HBM_PEAK_GBS, 4), 'traffic': traffic,
                     'ms_per_launch': round(dom_ms, 5), 'launches_per_step': round(per_step[dom] / dom_ms, 2) if dom_ms else None,
@@ -1100,17 +1147,7 @@ def main():
         if a.dtype != 'bf16' and kernels is None:
             # the kernel table above times the bf16 kernels: without an in-step trace (another profiler attached) an f32 run has no duration to put a roofline on
             roofline, roofline_detail = None, {'note': 'no in-step trace of the f32 step: see the rocprofv3 kernel statistics of this run'}
-        out = {
-            'metric': 'encounters/sec per joint interp+DEC step', 'value': round(value, 1), 'unit': 'encounters/s',
-            'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(ms, 3),
-            'higher_is_better': True, 'scaling': a.scaling, 'vs_baseline': None, 'dtype': a.dtype, 'data': 'synthetic',
-            'config': {'workload': workload, 'per_gpu_batch': a.batch, 'global_batch': a.batch * world, 'batches_per_epoch': nb,
-                       'encounters_stepped': world * rows_stepped, 'parallelism': f'dp{world}' if world > 1 else 'single',
-                       'index_order': 'shuffled' if shuffled else 'file order',
-                       'input': 'padded (B,4C,T) batches' if store is None else f'ragged encounter store read in place ({store.nbytes() / 1e6:.0f} MB resident)'},
-            'roofline': roofline,
-            'cpu_baseline': None,
-        }
+        out['roofline'] = roofline
         if world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(K, a.cpu_seconds)
         # ---- the contract line: the ONLY thing this program writes to stdout, written before any secondary record runs
@@ -1187,7 +1224,7 @@ def main():
                                                                                                           'library_gemm_ms', 'dominant_kernel', 'f32x3', 'error')})))
             sec.add('cfg5', guarded(record_cfg5, dev, not a.no_sweep))
         log('secondary records:', ', '.join(sec.paths))
-    elif world > 1:
+    elif world > 1 and a.full:
         # rank 0 traces n_trace more optimisation steps for the roofline record: a sharded step is full of collectives (loss
         # sums, BatchNorm moments, the gradient bucket), so every rank has to run them with it or rank 0 waits forever
         for i in range(n_trace):

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 STEPS=${2:-"1 2 3 4 5 6 7 8 9"}
 step1() {
   # 1. kernel statistics of the bench command itself
-  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -o b -- python3 $ROOT/bench.py --no-secondary --no-cpu-baseline --steps 30 --warmup 9 --kernel-iters 1 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -o b -- python3 $ROOT/bench.py --full --no-secondary --no-cpu-baseline --steps 30 --warmup 9 --kernel-iters 1 > $OUT/bench_under_rocprof.json 2> $OUT/bench_under_rocprof.err
   cp /tmp/p_stats/b_kernel_stats.csv $OUT/bench_kernel_stats.csv
   echo "[profile] kernel stats done"
 }
@@ -29,8 +29,8 @@ step2() {
 }
 step3() {
   # 3. HBM traffic of the whole step
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/s_fetch -o p -- python3 $ROOT/bench.py --no-secondary --no-cpu-baseline --steps 6 --warmup 3 --kernel-iters 1 > /dev/null 2>&1
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/s_write -o p -- python3 $ROOT/bench.py --no-secondary --no-cpu-baseline --steps 6 --warmup 3 --kernel-iters 1 > /dev/null 2>&1
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/s_fetch -o p -- python3 $ROOT/bench.py --full --no-secondary --no-cpu-baseline --steps 6 --warmup 3 --kernel-iters 1 > /dev/null 2>&1
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d /tmp/s_write -o p -- python3 $ROOT/bench.py --full --no-secondary --no-cpu-baseline --steps 6 --warmup 3 --kernel-iters 1 > /dev/null 2>&1
   python3 $ROOT/scripts/step_traffic.py /tmp/s_fetch/p_counter_collection.csv /tmp/s_write/p_counter_collection.csv $R > $OUT/step_traffic.txt
   cp $ROOT/profiles/step_traffic.json $OUT/step_traffic.json
   echo "[profile] step traffic done"
@@ -69,7 +69,7 @@ step7() {
 step8() {
   # 8. the f32 step with every dense product as a three-term bf16 split (--dtype f32x3) at the headline batch: kernel statistics + HBM traffic of its
   #    recurrence / product kernels (65 536 encounters = two FULL batches per epoch: every launch of the profiled run moves 32 768 encounters)
-  X3="--dtype f32x3 --encounters 65536 --no-secondary --no-cpu-baseline --kernel-iters 1"
+  X3="--dtype f32x3 --encounters 65536 --full --no-secondary --no-cpu-baseline --kernel-iters 1"
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/x3_stats -o k -- python3 $ROOT/bench.py $X3 --steps 10 --warmup 4 > $OUT/bench_f32x3_under_rocprof.json 2> /dev/null
   cp /tmp/x3_stats/k_kernel_stats.csv $OUT/step_f32x3_B32768_kernel_stats.csv
   rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d /tmp/x3_fetch -o p -- python3 $ROOT/bench.py $X3 --steps 4 --warmup 2 > /dev/null 2>&1

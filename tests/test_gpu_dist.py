@@ -444,7 +444,7 @@ def test_bench_runs_sharded_on_two_ranks(tmp_path):
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29533', os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--batch', '512',
-           '--encounters', '4096', '--no-secondary', '--no-cpu-baseline', '--kernel-iters', '1']
+           '--encounters', '4096', '--full', '--no-secondary', '--no-cpu-baseline', '--kernel-iters', '1']
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=root)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
@@ -626,7 +626,7 @@ def test_bench_runs_on_rccl_with_one_rank():
         env.pop(k, None)
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1',
            '--master-port', '29577', os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '512',
-           '--encounters', '4096', '--no-secondary', '--no-cpu-baseline', '--kernel-iters', '1']
+           '--encounters', '4096', '--full', '--no-secondary', '--no-cpu-baseline', '--kernel-iters', '1']
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     assert 'process group: nccl' in res.stderr, res.stderr[-2000:]
@@ -637,3 +637,33 @@ def test_bench_runs_on_rccl_with_one_rank():
                                                                      'vs_baseline', 'dtype', 'data', 'config', 'roofline', 'cpu_baseline'}
     side = json.load(open(os.path.join(ROOT, 'bench_secondary.json')))          # everything else goes to the side file
     assert side['headline']['value'] == rec['value'] and np.isfinite(side['whole_step']['final_loss']) and 'kernels' in side
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A plain ``bench.py --gpus 1`` (no --full): the contract line of exactly --steps timed steps, roofline / cpu_baseline null, and with
+    --dump-outputs the last timed step's loss terms, gradient norm, latents and parameters as float .npy files -- the same inputs on every run."""
+    import json
+    import subprocess
+    env = dict(os.environ)
+    for k in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT', 'DIC_DIST_BACKEND', 'DIC_DIST_SINGLE_RANK'):
+        env.pop(k, None)
+    dumps = []
+    for run in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '4', '--warmup', '2', '--batch', '512', '--encounters', '4096',
+               '--dump-outputs', str(tmp_path / run)]
+        res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=str(tmp_path))
+        assert res.returncode == 0, res.stderr[-2000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, res.stdout[-2000:]
+        rec = json.loads(lines[0])
+        assert rec['steps'] == 4 and rec['dtype'] == 'bf16' and rec['higher_is_better'] is True and rec['unit'] == 'encounters/s'
+        assert rec['roofline'] is None and rec['cpu_baseline'] is None and rec['config']['encounters_stepped'] == 4 * 512
+        assert abs(rec['value'] - 512 * 4 / (rec['ms_per_step'] * 4e-3)) <= 0.01 * rec['value']
+        d = {f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)}
+        assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in d.values())
+        assert {'losses.loss', 'losses.ae_mse', 'losses.kl', 'grad_norm', 'latents'} <= set(d) and d['latents'].shape[0] == 512
+        assert sum(v.nbytes for v in d.values()) <= 64 << 20 and any(k.startswith('params.encoder.lstm.') for k in d)
+        dumps.append(d)
+    assert set(dumps[0]) == set(dumps[1])
+    for k in dumps[0]:
+        np.testing.assert_allclose(dumps[1][k], dumps[0][k], rtol=1e-3, atol=1e-5, err_msg=k)

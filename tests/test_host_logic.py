@@ -89,6 +89,33 @@ def test_bench_secondary_records_go_to_a_side_file(tmp_path, monkeypatch, capsys
     assert all(len(ln) < 1700 for ln in cap.err.splitlines())
 
 
+def test_bench_dump_outputs_float_files_within_budget(tmp_path, monkeypatch, capsys):
+    """--dump-outputs: loss terms, gradient norm, parameters and buffers, latents as float32 / float64 .npy files; latents over the byte budget
+    keep a fixed seeded sample of rows (the same rows on every run), written beside them."""
+    import torch
+
+    import bench
+    net = torch.nn.Sequential(torch.nn.Linear(6, 4), torch.nn.BatchNorm1d(4))
+    losses = {'loss': torch.tensor(1.5), 'ae_mse': torch.tensor(0.5, requires_grad=True), 'kl': 0.1}
+    z = torch.randn(100, 8, dtype=torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / 'a'), losses, torch.tensor(2.0), z, net)
+    files = sorted(os.listdir(tmp_path / 'a'))
+    assert 'latents.npy' in files and 'latents_rows.npy' not in files and 'params.1.num_batches_tracked.npy' in files
+    for f in files:
+        assert np.load(tmp_path / 'a' / f).dtype in (np.float32, np.float64), f
+    assert float(np.load(tmp_path / 'a' / 'losses.ae_mse.npy')) == 0.5 and float(np.load(tmp_path / 'a' / 'grad_norm.npy')) == 2.0
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'latents.npy'), z.float().numpy())
+    np.testing.assert_array_equal(np.load(tmp_path / 'a' / 'params.0.weight.npy'), net[0].weight.detach().numpy())
+    monkeypatch.setattr(bench, 'DUMP_MAX_BYTES', 16 * 1024)
+    for d in ('b', 'c'):
+        bench.dump_outputs(str(tmp_path / d), losses, torch.tensor(2.0), torch.randn(4000, 8), net)
+    rows = np.load(tmp_path / 'b' / 'latents_rows.npy')
+    assert 0 < len(rows) < 4000 and np.all(np.diff(rows) > 0)
+    np.testing.assert_array_equal(rows, np.load(tmp_path / 'c' / 'latents_rows.npy'))
+    assert sum(os.path.getsize(tmp_path / 'b' / f) for f in os.listdir(tmp_path / 'b')) <= 16 * 1024
+    assert capsys.readouterr().out == ''
+
+
 def test_ragged_store_built_on_the_device_and_joined_equals_the_host_built_store():
     """RaggedStore.from_device / concat (cohorts too large to pad on the host) against the constructor on the same planes."""
     import torch
