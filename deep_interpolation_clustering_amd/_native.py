@@ -131,6 +131,9 @@ SIGNATURES = {
     'dic_kmeans_pp_workspace': (_sz, [_i, _i]),
     'dic_kmeans_pp_candidates': (_i, [_p, _i, _i, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
     'dic_kmeans_pp_candidates_rows': (_i, [_p, _i, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _sz, _p]),
+    'dic_dbscan_workspace': (_sz, [C.c_int64, _i]),
+    'dic_dbscan_counts': (_i, [_p, C.c_long, _p, C.c_int64, _i, _p, _i, _p, _p, C.c_int64, _p, _p, _sz, _p]),
+    'dic_dbscan_components_pass': (_i, [C.c_int64, _i, _f, _i, _p, _i, _p, C.c_int64, _p, _p, _p, _p, _sz, _p]),
 }
 
 

@@ -87,6 +87,7 @@ def _tile_list(counts_host):
 # by ~2^-17 |x - mean| |y - mean| (random sign), which the sums over thousands of pairs average away (tests: <= 2e-6 of a row's largest sum at 70 001 x 256) but
 # which shows on a handful of close points in few dimensions (4e-6 at 63 x 4) -- and below this size the difference-form kernel takes well under a millisecond.
 ROWSUM_MIN_POINTS = 8192
+PAIRDIST_MAX_K = 64         # dic_cluster_pairdist: clusters per pass
 ROWSUM_WORKGROUPS = 256     # dic_cluster_pair_rowsums: one persistent workgroup per CU, each a contiguous range of the tile list
 
 
@@ -171,8 +172,9 @@ def pair_stats(x, labels, need_min=True, need_max=True, intra_only=False):
         out[order] = S_own
         return PairStats(lab, counts, None, None, None, out)
     S = torch.empty((n, K), device=x.device, dtype=torch.float32)
-    if not need_min and not need_max and d <= TOTALS_MAX_D and n >= ROWSUM_MIN_POINTS:
-        # only the sums (the silhouette): the all-pairs pass on the matrix cores (dic_cluster_pair_rowsums), points relative to their mean
+    if not need_min and not need_max and d <= TOTALS_MAX_D and (n >= ROWSUM_MIN_POINTS or K > PAIRDIST_MAX_K):
+        # only the sums (the silhouette): the all-pairs pass on the matrix cores (dic_cluster_pair_rowsums), points relative to their mean -- also below
+        # ROWSUM_MIN_POINTS when dic_cluster_pairdist cannot take K (DBSCAN labellings, noise as a cluster of its own, often have more than 64)
         tiles, group_start, n_slots = _row_tile_list(counts.cpu().numpy(), n)
         tiles, group_start = torch.from_numpy(tiles).to(x.device), torch.from_numpy(group_start).to(x.device)
         centre = xs.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()

@@ -6,8 +6,11 @@
 Reads Results/Pretrain/out_feat/<metric>/<cohort>.npy (written by p1), writes
 Results/Pretrain/out_feat/<metric>_kmeans_aligned/plot/{elbow.csv, gap_sts_v1.csv}.  The gap statistic's
 "mean intra-cluster pairwise distance" and the validity indices come from one tiled all-pairs pass on the GPU
-(cluster_stats.py / csrc/dic_pairdist.hip) instead of an n_c x n_c float64 matrix per cluster (multi-GB at 75 k points).  DBSCAN / OPTICS and the seaborn plots of the
-upstream script are alternative algorithms / presentation and are not provided.
+(cluster_stats.py / csrc/dic_pairdist.hip) instead of an n_c x n_c float64 matrix per cluster (multi-GB at 75 k points).
+
+``--cluster_method dbscan`` (p2:82-85,90-168): DBSCAN for eps = 0.5, 1.0, .., 5.0 and min_samples = feat_dim + 1 on the GPU (dbscan.py: no N x N
+distance matrix), with the core / cluster / noise counts and both silhouettes per eps, written to <metric>_dbscan_aligned/plot/dbscan_eps.csv.  OPTICS,
+consensus, the k-distance graph with its elbow and the seaborn plots of the upstream script are not provided.
 """
 import argparse
 import os
@@ -20,6 +23,7 @@ import pandas as pd
 import torch
 
 from . import cluster_stats, dist
+from .dbscan import dbscan_sweep
 from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
 from .kmeans import KMeans, seed_draw_count
@@ -289,6 +293,47 @@ class KM(object):
         return out
 
 
+class Dbscan(object):
+    """Dbscan.train (p2:90-168): one DBSCAN per eps of ``eps_range`` on the training latents (one counting pass for all of them), logged as upstream logs
+    them; returns (and writes to plot/dbscan_eps.csv) the per-eps table."""
+    COLUMNS = ['eps', 'n_core', 'n_clusters', 'n_noise', 'silhouette', 'denoise_silhouette']
+
+    def __init__(self, eps_range, min_samples, out_path):
+        self.eps_range = eps_range
+        self.min_sample = min_samples
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+
+    def train(self, train_data, valid_data, select_eps, **kwargs):
+        train_feat = train_data['hidden']
+        if select_eps == 'k_distance_graph':
+            logger.info('select_eps k_distance_graph: the {}-NN distance plot and its elbow are not produced'.format(self.min_sample - 1))
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_feat, dtype=torch.float32, device=dev)
+        fits = dbscan_sweep(Xd, self.eps_range, self.min_sample)
+        rows = []
+        for eps, (labels, core) in zip(self.eps_range, fits):
+            logger.info('\nRunning eps: {}'.format(eps))
+            logger.info('core_sample: {}'.format(len(core)))
+            n_clusters_ = len(set(labels)) - (1 if -1 in labels else 0)
+            n_noise_ = int(np.sum(labels == -1))
+            logger.info('Estimated number of clusters: %d' % n_clusters_)
+            logger.info('Estimated number of noise points: %d' % n_noise_)
+            sil = sil_dn = float('nan')
+            if n_clusters_ == 1:
+                logger.info('Skip the Silhouette Coefficient calculation.')
+            elif n_clusters_ > 1:
+                keep = labels != -1
+                sil = cluster_stats.silhouette_score(Xd, labels)
+                sil_dn = cluster_stats.silhouette_score(Xd[torch.as_tensor(keep, device=dev)], labels[keep])
+                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(labels), sil))
+                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(int(keep.sum()), sil_dn))
+            rows.append([float(eps), len(core), n_clusters_, n_noise_, sil, sil_dn])
+        df = pd.DataFrame(rows, columns=self.COLUMNS)
+        df.to_csv(osp.join(self.out_path, 'dbscan_eps.csv'), index=False)
+        return df
+
+
 class Cluster(object):
     def __init__(self, args):
         self.args = args
@@ -310,8 +355,14 @@ class Cluster(object):
             self.out_path = osp.join(self.exp_path, 'out_feat', '{}_{}'.format(metric, self.args.cluster_method)) + '_aligned'
             os.makedirs(self.out_path, exist_ok=True)
             self.load_data()
+            if self.args.cluster_method == 'dbscan':
+                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
+                    eps_range = np.arange(.5, 5.1, .5)
+                    db = Dbscan(eps_range=eps_range, min_samples=self.feat_dim + 1, out_path=self.out_path)
+                    results[metric] = db.train(self.train_data, self.valid_data, self.args.select_eps)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans is on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans and dbscan are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

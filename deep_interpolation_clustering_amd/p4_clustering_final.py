@@ -3,8 +3,10 @@
 ``kmeans``: KMeans(k, n_init=20) on the training latents (HIP kernels), clusters re-numbered by descending mean
 systolic pressure so ids are comparable across runs (generate_align_map, p4:63-98), then ``predict`` on each cohort.
 ``dl``: argmax of the network's own soft assignment.  Reads Results/Clustering/out_feat/<metric>/<cohort>.npy,
-writes .../<metric>_<method>_aligned/<cohort>_<k>.npy with an added ``cluster_id``.  The dbscan / consensus
-branches of the upstream script are host-side alternatives and are not provided.
+writes .../<metric>_<method>_aligned/<cohort>_<k>.npy with an added ``cluster_id``.
+``dbscan`` (p4:181-236): a DBSCAN(opt_eps, min_samples = feat_dim) fit per cohort on the GPU (dbscan.py), training clusters re-numbered by
+sbp (generate_align_map), validation / test clusters mapped onto the nearest training centre (align_labels_with_center); writes
+<cohort>_eps-<opt_eps>.npy.  The consensus branch of the upstream script is not provided.
 """
 import argparse
 import copy
@@ -13,6 +15,8 @@ import os.path as osp
 
 import numpy as np
 
+from . import cluster_stats
+from .dbscan import DBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
 from .utils import logger, print_dict_byline
@@ -62,6 +66,60 @@ class Cluster(object):
         centers = [np.mean(feat[org_label == i], axis=0) for i in range(n_clusters)] if feat is not None else []
         return align_map, org_label, centers
 
+    def align_labels_with_center(self, org_feat, org_label, aligned_feat_centers):
+        """p4:113-139: each cluster of ``org_label`` takes the id of the nearest of ``aligned_feat_centers`` (the training clusters' centres); two clusters
+        mapped onto one centre raise ValueError.  Noise (-1) stays -1."""
+        n_clusters = len(set(org_label)) - (1 if -1 in org_label else 0)
+        org_centers = np.asarray([np.mean(org_feat[org_label == i], axis=0) for i in range(n_clusters)], dtype=np.float64)
+        ref = np.asarray(aligned_feat_centers, dtype=np.float64)
+        d = np.sqrt(np.maximum((org_centers ** 2).sum(1)[:, None] + (ref ** 2).sum(1)[None, :] - 2.0 * org_centers @ ref.T, 0.0))
+        min_dist_idx = np.argmin(d, axis=1)
+        if len(set(min_dist_idx)) != n_clusters:
+            logger.info(min_dist_idx)
+            raise ValueError('Different org_feat_centers map to a same train_feat_center')
+        align_map = {org_id: new_id for org_id, new_id in enumerate(min_dist_idx)}
+        logger.info('Align_map: {}'.format(align_map))
+        members = [np.where(org_label == i) for i in range(n_clusters)]
+        for org_id, new_id in align_map.items():
+            org_label[members[org_id]] = new_id
+        return org_label
+
+    def _dbscan(self, cohorts, overwrite):
+        opt_eps = self.args.opt_eps
+        logger.info('==> Generate the DBSCAN results with opt-eps: {}'.format(opt_eps))
+        train_feat_centers = None
+        for cohort, data in cohorts:
+            f = osp.join(self.out_path, '{}_eps-{}.npy'.format(cohort, opt_eps))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            logger.info('NEW DBSCAN model for {}'.format(cohort))
+            feat = data['hidden']
+            db = DBSCAN(opt_eps, feat.shape[-1]).fit(feat)
+            raw_label = db.labels_
+            if cohort == 'training':
+                _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
+            else:
+                aligned_label = self.align_labels_with_center(feat, raw_label, train_feat_centers)
+            data['cluster_id'] = aligned_label
+            del data['ob'], data['padding_mask']
+            logger.info('core_sample: {}'.format(len(db.core_sample_indices_)))
+            n_clusters_ = len(set(aligned_label)) - (1 if -1 in aligned_label else 0)
+            n_noise_ = int(np.sum(aligned_label == -1))
+            keep = aligned_label != -1
+            logger.info('Estimated number of clusters: %d' % n_clusters_)
+            logger.info('Estimated number of noise points: %d' % n_noise_)
+            if n_clusters_ == 0:
+                continue                      # (upstream writes nothing for this cohort either)
+            elif n_clusters_ == 1:
+                logger.info('Skip the Silhouette Coefficient calculation.')
+            else:
+                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(aligned_label), cluster_stats.silhouette_score(feat, aligned_label)))
+                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(
+                    int(keep.sum()), cluster_stats.silhouette_score(feat[keep], aligned_label[keep])))
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+            np.save(f, data)
+
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         for metric in self.args.restore_metric:
@@ -99,8 +157,10 @@ class Cluster(object):
                         continue
                     np.save(f, data)
                     logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+            elif self.args.cluster_method == 'dbscan':
+                self._dbscan(cohorts, overwrite)
             else:
-                raise NotImplementedError("only 'kmeans' and 'dl' are on the accelerated path")
+                raise NotImplementedError("only 'kmeans', 'dl' and 'dbscan' are on the accelerated path")
 
 
 def main(args):

@@ -591,6 +591,28 @@ int dic_gemm_nt_planes(const void* A_hi, long a_plane, long lda, const float* W,
 int dic_gemm_tn_planes(const void* A_hi, long a_plane, long lda, const float* X, long ldx, long M, int N, int K, float* D, long ldd, int kcols,
                        const float* X2, long ldx2, int K2, float* D2, long ldd2, int accumulate, int relu_x, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* DBSCAN without the distance matrix (csrc/dic_dbscan.hip): p2_clustering_optK.py:82-85,90-168 and p4_clustering_final.py:181-236 build
+ * pairwise_distances(X) and fit DBSCAN(eps, min_samples, metric='precomputed') on it; these recompute the distances tile by tile on the matrix cores.
+ * X (N, D) f32 at row stride ldx, D <= 256, D % 4 == 0 (zero-pad narrower points), N < 2^30, 16-B aligned.  Neighbour rule (sklearn's): (i, j) are
+ * neighbours for eps e iff f32(||x_i - x_j||^2) <= thresholds[e], thresholds[e] the largest f32 s with sqrt_f32(s) <= eps under NumPy's promotion of the
+ * caller's eps (dbscan.py); the self pair counts.  One workspace (dic_dbscan_workspace(N, D) bytes) serves the counting pass and, unchanged, every
+ * components pass after it (it holds the split planes of the points).
+ *   dic_dbscan_counts: counts (n_eps, N) int32 OVERWRITTEN = |N_eps(i)| for every eps (n_eps <= 16) in ONE pair pass; centre (1, D) f32 = the mean of the
+ *       points.  A pair whose approximate d^2 lies within the derived error bound of some threshold is a BAND pair: appended to band (capacity, 4) int32 as
+ *       (i, j, neighbour mask, 0) and decided exactly (f64 difference form) by a second kernel.  *n_band (host) = the number of band pairs found; more than
+ *       `capacity` returns DIC_ERR_WORKSPACE (counts incomplete; run again with capacity >= *n_band).  Reads *n_band back: synchronises `stream`.
+ *   dic_dbscan_components_pass: one label pass of eps eps_index (threshold = thresholds[eps_index]) over the core graph, core = counts_e[i] >= min_samples
+ *       (counts_e = row eps_index of counts; band / n_band as dic_dbscan_counts left them).  labels (N) int32, initialised by the caller to 0..N-1: every
+ *       core point takes the smallest label of its core neighbours and hooks its root to it (atomicMin), then labels jump to their roots.  *changed (device
+ *       int32, zeroed by the caller) is set to 1 when a label moved.  border (N) int32 OVERWRITTEN: for a non-core point, the smallest label among its core
+ *       neighbours (0x7f7f7f7f: none).  Repeat until a pass leaves *changed at 0; then labels[i] (core i) = the smallest core index of i's component and
+ *       border holds, per border point, the root of its smallest-numbered neighbouring cluster (sklearn's _dbscan_inner).  Deterministic results. */
+size_t dic_dbscan_workspace(int64_t N, int D);
+int dic_dbscan_counts(const float* X, long ldx, const float* centre, int64_t N, int D, const float* thresholds, int n_eps, int32_t* counts, int32_t* band,
+                      int64_t capacity, int64_t* n_band, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_dbscan_components_pass(int64_t N, int D, float threshold, int eps_index, const int32_t* counts_e, int min_samples, const int32_t* band, int64_t n_band,
+                               int32_t* labels, int32_t* border, int32_t* changed, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
