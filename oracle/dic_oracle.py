@@ -219,9 +219,33 @@ class _PerStep(nn.Module):
         return out.reshape(x.shape[0], -1, out.shape[-1])
 
 
+def tapped_relu(taps, site, a):
+    """relu(a).  ``taps`` (None, or a dict the caller owns) makes the kink observable: ``taps['pre'][site]`` receives the pre-activation, and
+    ``taps['flip'][site]`` (a bool tensor, optional) names elements whose derivative mask is inverted -- the gradient an implementation gets
+    whose own rounding puts an |a| ~ 1e-6 pre-activation on the other side of zero (oracle/step_grads.py: the kink term)."""
+    if taps is None:
+        return F.relu(a)
+    taps.setdefault('pre', {})[site] = a.detach()
+    flip = (taps.get('flip') or {}).get(site)
+    if flip is None:
+        return F.relu(a)
+    return a * ((a.detach() > 0) ^ flip).to(a.dtype)
+
+
+class _TapReLU(nn.Module):
+    """nn.ReLU of CompressFC, observable through the owning net's ``taps`` (site 'compress')."""
+
+    def __init__(self):
+        super().__init__()
+        self.owner = None                 # a one-element list holding the OracleNet (not a submodule: no cycle in the module tree)
+
+    def forward(self, a):
+        return tapped_relu(self.owner[0].taps if self.owner else None, 'compress', a)
+
+
 def _compress_fc(idim, odim, p):
     """rbf.py:111-125."""
-    return _Seq(nn.Linear(idim, 128), nn.BatchNorm1d(128), nn.ReLU(), nn.Dropout(p), nn.Linear(128, odim))
+    return _Seq(nn.Linear(idim, 128), nn.BatchNorm1d(128), _TapReLU(), nn.Dropout(p), nn.Linear(128, odim))
 
 
 def _head(idim, odim, p, tail=None):
@@ -251,6 +275,17 @@ class _Rbf(nn.Module):
         self.kernel = nn.Parameter(torch.rand(C))
 
 
+def _by_encounters(chunk, fn, *batched):
+    """``fn`` over pieces of ``chunk`` encounters, each under activation checkpointing.  The interpolation layers act on one encounter at a
+    time and their (B,C,T,R) temporaries are what a large batch costs in memory (35 GB in f64 at B = 4160, C = 12, T = 288): in pieces they
+    are rebuilt during the backward instead of kept.  Same operations on the same rows; ``chunk=None`` is the plain call."""
+    B = batched[0].shape[0]
+    if not chunk or B <= chunk:
+        return fn(*batched)
+    from torch.utils.checkpoint import checkpoint
+    return torch.cat([checkpoint(fn, *(t[i:i + chunk] for t in batched), use_reentrant=False) for i in range(0, B, chunk)], dim=0)
+
+
 class OracleNet(nn.Module):
     """clustering_interp.Net (clustering_interp.py:89-247) / pretrain_interp.Net
     restated on the oracle ops, with upstream ``state_dict`` key names so golden
@@ -263,6 +298,8 @@ class OracleNet(nn.Module):
         C = num_variables
         self.C, self.R, self.H = C, ref_points, hours
         self.fake_detection = fake_detection
+        self.taps = None              # see tapped_relu: the two ReLUs of the forward ('context', 'compress') made observable
+        self.chunk = None             # encounters per checkpointed piece of the interpolation layers (None: whole batch at once); see _by_encounters
         self.aux_tasks = dict(aux_tasks or {})
         self.clustering = clustering
         self.sci = _Param('kernel', torch.rand(C))
@@ -270,6 +307,7 @@ class OracleNet(nn.Module):
         self.encoder = _Lstm(3 * C, 128)
         self.decoder = _Lstm(256, 128)
         self.rbf = _Rbf(C, dropout)
+        self.rbf.compress_fc.module.model[2].owner = [self]
         n_aux = len(self.aux_tasks)
         if 'future_vital' in self.aux_tasks:
             self.predict_future = _head(256, C, dropout, nn.Sigmoid())
@@ -284,15 +322,15 @@ class OracleNet(nn.Module):
             self.cluster_assignment = _Param('cluster_centers', centers)
 
     def encode(self, x):
-        feats = sci_cci_forward(x, self.sci.kernel, self.cci.kernel, self.R, self.H)
+        feats = _by_encounters(self.chunk, lambda xs: sci_cci_forward(xs, self.sci.kernel, self.cci.kernel, self.R, self.H), x)
         context, (h, c) = self.encoder.lstm(feats.permute(1, 0, 2))
         return context, h, c, torch.cat([h[0], h[1]], dim=-1)
 
     def forward(self, x, fake_x=None, fake_perm_idx=None, positive_x=None):
         context, h, c, z = self.encode(x)
-        dec_out, _ = self.decoder.lstm(F.relu(context), (h, c))          # clustering_interp.py:38-41
+        dec_out, _ = self.decoder.lstm(tapped_relu(self.taps, 'context', context), (h, c))          # clustering_interp.py:38-41
         v = self.rbf.compress_fc(dec_out.permute(1, 0, 2)).permute(0, 2, 1)   # (B,C,R)
-        y = rbf_deinterp(v, x, self.rbf.kernel, self.R, self.H)
+        y = _by_encounters(self.chunk, lambda vs, xs: rbf_deinterp(vs, xs, self.rbf.kernel, self.R, self.H), v, x)
         aux = {}
         if 'future_vital' in self.aux_tasks:
             aux['future_vital'] = self.predict_future(z)

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from oracle import dic_oracle as O
+from oracle.step_grads import fixture_gradient_misses
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), 'golden')
@@ -65,6 +66,13 @@ def test_joint_step_matches_reference(name, use_lengths):
         np.testing.assert_allclose(float(losses['fake_detection']), float(g['loss_fake_detection']), rtol=1e-5)
     np.testing.assert_allclose(z.detach().cpu().numpy(), g['z'], rtol=1e-4, atol=2e-6)
     np.testing.assert_allclose(float(gnorm), float(g['gnorm']), rtol=1e-4)
+    # the reference's own full gradients (g/<name>, every small tensor): the bucket after a step whose norm stays below the clip is the unscaled gradient
+    assert float(g['gnorm']) < args.grad_clip
+    # (the bias in front of the BatchNorm: true gradient zero; at B = 16, R = 12 the reference's own f32 value is 5e-7 of gnorm and 1e-6 is not available
+    #  in f32 -- 50 x the reference's own noise there, the rule of tests/test_gpu_step_grads.py for these two fixtures)
+    noise = float(np.linalg.norm(g['g/rbf.compress_fc.module.model.0.bias'].astype(np.float64))) / float(g['gnorm'])
+    bad = fixture_gradient_misses({k: p.grad for k, p in net.named_parameters()}, g, 1e-4, null_bar=50 * noise)
+    assert not bad, bad
     # parameters after clip + Adam(amsgrad, wd): compare where the gradient is decisively non-zero
     for k, v in net.state_dict().items():
         got = v.detach().cpu().numpy()

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+from oracle.step_grads import fixture_gradient_misses
+
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(__file__), 'golden')
 
@@ -168,6 +170,10 @@ def test_joint_step_cfg_shape_kmeans_centroids(K, use_lengths):
     for k in ('loss', 'ae_mse', 'kl'):
         np.testing.assert_allclose(float(losses[k]), float(g['loss_' + k]), rtol=1e-5, atol=0, err_msg=k)
     np.testing.assert_allclose(float(gnorm), float(g['gnorm']), rtol=1e-4)
+    # the reference's own full gradients (g/<name>, every small tensor): the bucket after a step whose norm stays below the clip is the unscaled gradient
+    assert float(g['gnorm']) < args.grad_clip
+    bad = fixture_gradient_misses({k: p.grad for k, p in net.named_parameters()}, g, 1e-4)
+    assert not bad, bad
     np.testing.assert_allclose(z.detach().cpu().numpy(), g['z'], rtol=1e-4, atol=2e-6)
     q = net.cluster_assignment(z.detach())
     assert (q.argmax(1).cpu().numpy() == g['q'].argmax(1)).all()
@@ -216,6 +222,10 @@ def test_joint_step_wide_shape_K16(inp):
     for k in ('loss', 'ae_mse', 'kl'):
         np.testing.assert_allclose(float(losses[k]), float(g['loss_' + k]), rtol=1e-5, atol=0, err_msg=k)
     np.testing.assert_allclose(float(gnorm), float(g['gnorm']), rtol=1e-4)
+    # the reference's own full gradients (g/<name>, every small tensor): the bucket after a step whose norm stays below the clip is the unscaled gradient
+    assert float(g['gnorm']) < args.grad_clip
+    bad = fixture_gradient_misses({k: p.grad for k, p in net.named_parameters()}, g, 1e-4)
+    assert not bad, bad
     np.testing.assert_allclose(z.detach().cpu().numpy(), g['z'], rtol=1e-4, atol=2e-6)
     q = net.cluster_assignment(z.detach())
     assert (q.argmax(1).cpu().numpy() == g['q'].argmax(1)).all()
