@@ -1,0 +1,296 @@
+// The pair-tile machine of dic_dbscan.hip as a header: the split-bf16 planes of the centred points, their layout in a workspace, and the persistent 256 x 256
+// tile loop, whose result -- the approximate d^2 of 2 x 64 (i, j) pairs per lane, in registers -- goes to an epilogue the caller supplies.  The planes, the
+// products and hence the error bound of that d^2 are those derived at the top of dic_dbscan.hip (B0 = 2^-12 (n_i + nmax_J)); nothing here decides anything.
+// dic_knn.hip is built on it.  dic_dbscan.hip keeps its own copy of the loop: moving its kernels onto this header changes their register allocation.
+#pragma once
+#include "dic_common.h"
+
+namespace dic {
+
+typedef __bf16 pbf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 pbf16x4 __attribute__((ext_vector_type(4)));
+typedef float pf32x16 __attribute__((ext_vector_type(16)));
+typedef float pf32x4 __attribute__((ext_vector_type(4)));
+typedef int pi32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int PT_D = 256;                              // coordinates (narrower inputs are zero-padded by the caller to a multiple of 4)
+constexpr int PT_LD = 288;                             // columns of an augmented row
+constexpr int PT_T = 256;                              // points per tile edge
+constexpr int PT_K = 32;                               // columns per slab
+constexpr int PT_ROWB = PT_K * 2;                      // 64 B
+constexpr int PT_PLANE = PT_T * PT_ROWB;               // 16 KB: one plane of a slab
+constexpr int PT_SLOT = 2 * PT_PLANE;                  // 32 KB: hi | lo
+constexpr int PT_SLABS = PT_LD / PT_K;                 // 9
+constexpr int PT_NI = 3, PT_NJ = 2;                    // ring depths of the two operands
+constexpr int PT_LDS = (PT_NI + PT_NJ) * PT_SLOT;      // 163 840 B
+static_assert(PT_LDS <= 160 * 1024, "pair tiles: LDS budget");
+
+// Workspace of the planes: pa / pb (hi | lo planes of the two operands, N + 256 rows each), the f32 norms (N + 256), the largest norm of every 256-row block,
+// and one 256-B scratch word block for the caller.
+struct PtLayout { size_t pa, pb, nrm, bmax, count, total; };
+
+inline PtLayout pt_layout(int64_t N) {
+    PtLayout o;
+    const size_t plane = (size_t)(N + PT_T) * PT_LD * sizeof(__bf16);
+    const size_t nblk = (size_t)((N + PT_T - 1) / PT_T);
+    o.pa = 0;
+    o.pb = o.pa + align_up(2 * plane, 256);
+    o.nrm = o.pb + align_up(2 * plane, 256);
+    o.bmax = o.nrm + align_up((size_t)(N + PT_T) * sizeof(float), 256);
+    o.count = o.bmax + align_up(nblk * sizeof(float), 256);
+    o.total = o.count + 256;
+    return o;
+}
+
+// What the tile loop reads.  The tiles are the ordered block pairs (I, J), row-major; a launch walks tiles tile0 .. tile0 + ntiles - 1 (a run of whole row
+// blocks I when tile0 and ntiles are multiples of nblk), split evenly over its workgroups.
+struct PtPairArgs {
+    const __bf16* pa; const __bf16* pb; long plane;
+    const float* nrm; const float* bmax;
+    int n, nblk; long long tile0, ntiles;
+};
+
+inline void pt_fill_pair_args(PtPairArgs& t, unsigned char* ws, int64_t N) {
+    const PtLayout o = pt_layout(N);
+    t.pa = (const __bf16*)(ws + o.pa);
+    t.pb = (const __bf16*)(ws + o.pb);
+    t.plane = (long)((N + PT_T) * PT_LD);
+    t.nrm = (const float*)(ws + o.nrm);
+    t.bmax = (const float*)(ws + o.bmax);
+    t.n = (int)N;
+    t.nblk = (int)((N + PT_T - 1) / PT_T);
+    t.tile0 = 0;
+    t.ntiles = (long long)t.nblk * t.nblk;
+}
+
+inline unsigned pt_grid(long long ntiles) { return (unsigned)(ntiles < 1 ? 1 : ntiles < (long long)kNumCU ? ntiles : (long long)kNumCU); }
+
+// Augmented rows relative to one centre, and the f32 norms.  One wave per point: lane l holds coordinates 4 l .. 4 l + 3.
+static __global__ __launch_bounds__(256) void pt_prep_kernel(const float* X, long ldx, const float* mu, int n, int d, __bf16* pa, __bf16* pb, long plane, float* nrm_out) {
+    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= n) return;
+    const int col = 4 * lane;
+    pf32x4 v = {0.f, 0.f, 0.f, 0.f};
+    if (col < d) {
+        const pf32x4 x = *reinterpret_cast<const pf32x4*>(X + (size_t)row * ldx + col);
+        const pf32x4 m = *reinterpret_cast<const pf32x4*>(mu + col);
+        v = x - m;
+    }
+    float nrm = fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], v[3] * v[3])));
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) nrm += __shfl_xor(nrm, o);
+    pbf16x4 ah, al, bh, bl;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const __bf16 h = (__bf16)v[e];
+        const __bf16 l = (__bf16)(v[e] - (float)h);
+        ah[e] = h; al[e] = l;
+        bh[e] = (__bf16)(-2.f * (float)h); bl[e] = (__bf16)(-2.f * (float)l);          // exact
+    }
+    const size_t at = (size_t)row * PT_LD + col;
+    *reinterpret_cast<pbf16x4*>(pa + at) = ah;
+    *reinterpret_cast<pbf16x4*>(pa + plane + at) = al;
+    *reinterpret_cast<pbf16x4*>(pb + at) = bh;
+    *reinterpret_cast<pbf16x4*>(pb + plane + at) = bl;
+    if (lane < 8) {                                     // columns 256 + 4 lane ..: [n n n 1 | 1 1 0 0 | 0 ..] and [1 1 1 n | n n 0 0 | 0 ..]
+        const __bf16 n0 = (__bf16)nrm;
+        const float r1 = nrm - (float)n0;
+        const __bf16 n1 = (__bf16)r1;
+        const __bf16 n2 = (__bf16)(r1 - (float)n1);
+        const __bf16 one = (__bf16)1.f, z = (__bf16)0.f;
+        pbf16x4 ea = {z, z, z, z}, eb = {z, z, z, z};
+        if (lane == 0) { ea = pbf16x4{n0, n1, n2, one}; eb = pbf16x4{one, one, one, n0}; }
+        if (lane == 1) { ea = pbf16x4{one, one, z, z}; eb = pbf16x4{n1, n2, z, z}; }
+        const size_t et = (size_t)row * PT_LD + PT_D + 4 * lane;
+        const pbf16x4 zz = {z, z, z, z};
+        *reinterpret_cast<pbf16x4*>(pa + et) = ea;
+        *reinterpret_cast<pbf16x4*>(pa + plane + et) = zz;
+        *reinterpret_cast<pbf16x4*>(pb + et) = eb;
+        *reinterpret_cast<pbf16x4*>(pb + plane + et) = zz;
+    }
+    if (lane == 0) nrm_out[row] = nrm;
+}
+
+// largest norm of every 256-row block (norms are >= 0; rows past n count 0)
+static __global__ __launch_bounds__(256) void pt_block_max_kernel(const float* nrm, int n, float* bmax) {
+    __shared__ float part[4];
+    const int i = blockIdx.x * PT_T + threadIdx.x;
+    float v = i < n ? nrm[i] : 0.f;
+    v = wave_max(v);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) bmax[blockIdx.x] = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
+}
+
+// the 256 padding points as operand j: norm `pad_norm` (a power of two: exact in bf16) in the first norm column of pb
+static __global__ __launch_bounds__(256) void pt_pad_norm_kernel(__bf16* pb, int n, float pad_norm) {
+    pb[(size_t)(n + threadIdx.x) * PT_LD + PT_D + 3] = (__bf16)pad_norm;
+}
+
+// Fills the planes, norms and block maxima of a pt_layout(N) workspace from X (N, D) f32 and the centre (1, D).  The 256 padding rows behind the last point,
+// which the last tiles read, are zero vectors of norm 0 as operand i; as operand j they present the norm pad_norm, so their approximate d^2 is n_i + pad_norm:
+// with 0 an epilogue masks them by index, with a huge value they lie beyond every threshold and need no mask.  (The norm array and the block maxima, which
+// feed the error bound, hold 0 for them either way.)
+static int pt_prepare_planes(const float* X, long ldx, const float* centre, int64_t N, int D, float pad_norm, unsigned char* ws, hipStream_t st,
+                             const char* who) {
+    const PtLayout o = pt_layout(N);
+    const long plane = (long)((N + PT_T) * PT_LD);
+    __bf16* pa = (__bf16*)(ws + o.pa);
+    __bf16* pb = (__bf16*)(ws + o.pb);
+    float* nrm = (float*)(ws + o.nrm);
+    hipError_t e = hipMemsetAsync(pa + (size_t)N * PT_LD, 0, (size_t)PT_T * PT_LD * sizeof(__bf16), st);
+    if (e == hipSuccess) e = hipMemsetAsync(pa + plane + (size_t)N * PT_LD, 0, (size_t)PT_T * PT_LD * sizeof(__bf16), st);
+    if (e == hipSuccess) e = hipMemsetAsync(pb + (size_t)N * PT_LD, 0, (size_t)PT_T * PT_LD * sizeof(__bf16), st);
+    if (e == hipSuccess) e = hipMemsetAsync(pb + plane + (size_t)N * PT_LD, 0, (size_t)PT_T * PT_LD * sizeof(__bf16), st);
+    if (e == hipSuccess) e = hipMemsetAsync(nrm + N, 0, (size_t)PT_T * sizeof(float), st);
+    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
+    if (pad_norm != 0.f) hipLaunchKernelGGL(pt_pad_norm_kernel, dim3(1), dim3(256), 0, st, pb, (int)N, pad_norm);
+    hipLaunchKernelGGL(pt_prep_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, X, ldx, centre, (int)N, D, pa, pb, plane, nrm);
+    const int nblk = (int)((N + PT_T - 1) / PT_T);
+    hipLaunchKernelGGL(pt_block_max_kernel, dim3(nblk), dim3(256), 0, st, (const float*)nrm, (int)N, (float*)(ws + o.bmax));
+    return DIC_OK;
+}
+
+__device__ __forceinline__ void ptdma16(const void* sbase, unsigned voff, unsigned lds_dst) {
+    unsigned keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
+}
+
+// Where a lane sits in its 8-wave workgroup: wave (wm, wn) owns rows 64 wm .. + 63 and columns 128 wn .. + 127 of the tile; the lane holds rows
+// 64 wm + 32 mb + l31 (mb = 0, 1) and, of accumulator acc[nb][mb][k], column 128 wn + 32 nb + 4 hh + (k & 3) + 8 (k >> 2).
+struct PtLane {
+    int lane, hh, l31, wm, wn;
+    __device__ __forceinline__ PtLane() {
+        lane = threadIdx.x & 63; hh = lane >> 5; l31 = lane & 31;
+        const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+        wm = w & 3; wn = w >> 2;
+    }
+    __device__ __forceinline__ int row(int I0, int mb) const { return I0 + 64 * wm + 32 * mb + l31; }
+    __device__ __forceinline__ int col(int J0, int nb, int k) const { return J0 + 128 * wn + 32 * nb + 4 * hh + (k & 3) + 8 * (k >> 2); }
+};
+
+// The persistent tile loop (launch with 512 threads, PT_LDS bytes of dynamic LDS, __launch_bounds__(512, 1)).  For every tile of the workgroup's range, in
+// order: epi.finish(I0, J0, acc) with acc[nb][mb][k] = the approximate d^2 of (PtLane::row(I0, mb), PtLane::col(J0, nb, k)); after the last one epi.flush().
+// An epilogue keeps its per-row results in registers while I0 stays the same and flushes them itself when it changes.
+template <class Epi>
+__device__ __forceinline__ void pt_pair_pass(const PtPairArgs& a, Epi& epi) {
+    extern __shared__ __align__(16) unsigned char dsm[];
+    const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, l31 = lane & 31;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), wm = w & 3, wn = w >> 2;
+    const long long nch = gridDim.x;
+    const long long per = (a.ntiles + nch - 1) / nch;
+    const long long first = (long long)blockIdx.x * per;
+    const long long my_tiles = max(0LL, min(per, a.ntiles - first));
+    const long long S = my_tiles * PT_SLABS;
+    if (S == 0) return;
+    const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) unsigned char*)dsm);
+    const unsigned ldsI = lds0, ldsJ = lds0 + PT_NI * PT_SLOT;
+    const unsigned v_dma = (unsigned)(lane >> 2) * (PT_LD * 2) + (unsigned)(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
+    // tile t of the range: (first row of I, first row of J), row-major over the block pairs
+    auto tile = [&](long long i) {
+        const long long t = a.tile0 + first + min(i, my_tiles - 1);
+        const int bi = (int)(t / a.nblk), bj = (int)(t - (long long)bi * a.nblk);
+        pi32x4 r;
+        r[0] = __builtin_amdgcn_readfirstlane(bi * PT_T);
+        r[1] = __builtin_amdgcn_readfirstlane(bj * PT_T);
+        r[2] = 0; r[3] = 0;
+        return r;
+    };
+    pi32x4 e_cur = tile(0), e_nxt = tile(1), e_prev = e_cur;
+    long long cur_tile = 0;
+    auto issue = [&](const __bf16* mat, int row0, int ks, unsigned dst) {
+        const __bf16* src = mat + (size_t)row0 * PT_LD + ks * PT_K;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int c = w + 8 * j, pl = c >> 4, rg = c & 15;
+            const uint64_t p = (uint64_t)(src + (size_t)pl * a.plane + (size_t)(16 * rg) * PT_LD);          // (uniform: keep the base in scalar registers)
+            const uint64_t q = ((uint64_t)__builtin_amdgcn_readfirstlane((unsigned)(p >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((unsigned)p);
+            ptdma16((const void*)q, v_dma, __builtin_amdgcn_readfirstlane(dst + pl * PT_PLANE + rg * 1024));
+        }
+    };
+    auto issue_i = [&](long long s) { issue(a.pa, s / PT_SLABS == cur_tile ? e_cur[0] : e_nxt[0], (int)(s % PT_SLABS), ldsI + (int)(s % PT_NI) * PT_SLOT); };
+    auto issue_j = [&](long long s) { issue(a.pb, s / PT_SLABS == cur_tile ? e_cur[1] : e_nxt[1], (int)(s % PT_SLABS), ldsJ + (int)(s % PT_NJ) * PT_SLOT); };
+    const int sw = (l31 >> 2) & 3;
+    int poff[PT_K / 16];
+#pragma unroll
+    for (int kk = 0; kk < PT_K / 16; ++kk) poff[kk] = ((2 * kk + hh) ^ sw) * 16;
+    const int j_row = (128 * wn + l31) * PT_ROWB;
+    const int i_row = (64 * wm + l31) * PT_ROWB;
+
+#pragma unroll
+    for (int it = 1 - PT_NI; it < 0; ++it) {
+        if (it + PT_NJ - 1 >= 0 && it + PT_NJ - 1 < S) issue_j(it + PT_NJ - 1);
+        if (it + PT_NI - 1 < S) issue_i(it + PT_NI - 1);
+    }
+    pf32x16 acc[4][2];
+    for (long long s = 0; s < S; ++s) {
+        const int ks = (int)(s % PT_SLABS);
+        if (ks == 0 && s > 0) {
+            e_prev = e_cur;
+            e_cur = e_nxt;
+            ++cur_tile;
+            e_nxt = tile(cur_tile + 1);
+        }
+        if (S - 1 - s >= PT_NI - 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        const unsigned char* A = dsm + PT_NI * PT_SLOT + (int)(s % PT_NJ) * PT_SLOT + j_row;
+        const unsigned char* Bm = dsm + (int)(s % PT_NI) * PT_SLOT + i_row;
+        pbf16x8 ah[2][4], bh[2][2], al[4], bl[2];
+        auto load_hi = [&](int kk, int set) {
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) bh[set][mb] = *reinterpret_cast<const pbf16x8*>(Bm + mb * 32 * PT_ROWB + poff[kk]);
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) ah[set][nb] = *reinterpret_cast<const pbf16x8*>(A + nb * 32 * PT_ROWB + poff[kk]);
+        };
+        auto load_lo = [&](int kk) {
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) bl[mb] = *reinterpret_cast<const pbf16x8*>(Bm + PT_PLANE + mb * 32 * PT_ROWB + poff[kk]);
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb) al[nb] = *reinterpret_cast<const pbf16x8*>(A + PT_PLANE + nb * 32 * PT_ROWB + poff[kk]);
+        };
+        load_hi(0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        if (s + PT_NJ - 1 < S) issue_j(s + PT_NJ - 1);
+        if (s + PT_NI - 1 < S) issue_i(s + PT_NI - 1);
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks == 0) {
+            if (s > 0) epi.finish(e_prev[0], e_prev[1], acc);
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+                    for (int k = 0; k < 16; ++k) acc[nb][mb][k] = 0.f;
+        }
+        const bool coords = ks < PT_D / PT_K;
+#pragma unroll
+        for (int kk = 0; kk < PT_K / 16; ++kk) {
+            if (coords) load_lo(kk);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb) acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk & 1][nb], bh[kk & 1][mb], acc[nb][mb], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (kk + 1 < PT_K / 16) load_hi(kk + 1, (kk + 1) & 1);
+            __builtin_amdgcn_sched_barrier(0);
+            if (coords) {
+#pragma unroll
+                for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+                    for (int mb = 0; mb < 2; ++mb) {
+                        acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[nb], bh[kk & 1][mb], acc[nb][mb], 0, 0, 0);
+                        acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk & 1][nb], bl[mb], acc[nb][mb], 0, 0, 0);
+                    }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    epi.finish(e_cur[0], e_cur[1], acc);
+    epi.flush();
+}
+
+}  // namespace dic

@@ -9,8 +9,10 @@ Results/Pretrain/out_feat/<metric>_kmeans_aligned/plot/{elbow.csv, gap_sts_v1.cs
 (cluster_stats.py / csrc/dic_pairdist.hip) instead of an n_c x n_c float64 matrix per cluster (multi-GB at 75 k points).
 
 ``--cluster_method dbscan`` (p2:82-85,90-168): DBSCAN for eps = 0.5, 1.0, .., 5.0 and min_samples = feat_dim + 1 on the GPU (dbscan.py: no N x N
-distance matrix), with the core / cluster / noise counts and both silhouettes per eps, written to <metric>_dbscan_aligned/plot/dbscan_eps.csv.  OPTICS,
-consensus, the k-distance graph with its elbow and the seaborn plots of the upstream script are not provided.
+distance matrix), with the core / cluster / noise counts and both silhouettes per eps, written to <metric>_dbscan_aligned/plot/dbscan_eps.csv.  With
+--select_eps k_distance_graph (the default; p2:102-120) the feat_dim-NN distance curve of the training latents and its elbow -- the eps p4's --opt_eps is
+meant to be -- go to plot/k_distance.csv and plot/k_distance_elbow.csv (knn.py).  OPTICS, consensus and the seaborn plots of the upstream script are not
+provided.
 """
 import argparse
 import os
@@ -27,6 +29,7 @@ from .dbscan import dbscan_sweep
 from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
 from .kmeans import KMeans, seed_draw_count
+from .knn import k_distance_graph
 from .utils import logger, print_dict_byline
 
 np.random.seed(123)        # p2_clustering_optK.py:23
@@ -295,7 +298,9 @@ class KM(object):
 
 class Dbscan(object):
     """Dbscan.train (p2:90-168): one DBSCAN per eps of ``eps_range`` on the training latents (one counting pass for all of them), logged as upstream logs
-    them; returns (and writes to plot/dbscan_eps.csv) the per-eps table."""
+    them; returns (and writes to plot/dbscan_eps.csv) the per-eps table.  ``select_eps == 'k_distance_graph'`` (p2:102-120) first writes the
+    (min_samples - 1)-NN distance curve (plot/k_distance.csv: sample, dist) and its elbow (plot/k_distance_elbow.csv: k, elbow_x, elbow_y) and keeps them
+    on ``k_distance_``; an existing k_distance.csv is left alone unless ``overwrite`` is set, as upstream leaves its plot."""
     COLUMNS = ['eps', 'n_core', 'n_clusters', 'n_noise', 'silhouette', 'denoise_silhouette']
 
     def __init__(self, eps_range, min_samples, out_path):
@@ -303,13 +308,30 @@ class Dbscan(object):
         self.min_sample = min_samples
         self.out_path = osp.join(out_path, 'plot')
         os.makedirs(self.out_path, exist_ok=True)
+        self.k_distance_ = None
+
+    def k_distance(self, Xd, overwrite=False):
+        """p2:102-120 on the device copy of the latents: the k-distance table, its elbow, the log line."""
+        k = self.min_sample - 1
+        csv = osp.join(self.out_path, 'k_distance.csv')
+        if osp.exists(csv) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(csv))
+            return None
+        graph = k_distance_graph(Xd, k)
+        sorted_dist = graph['sorted_dist']
+        logger.info('The detected elbow: x: {}, y: {}'.format(graph['elbow_x'], graph['elbow_y']))
+        pd.DataFrame({'sample': np.arange(1, len(sorted_dist) + 1), 'dist': sorted_dist}).to_csv(csv, index=False, float_format='%.17g')
+        pd.DataFrame({'k': [k], 'elbow_x': [graph['elbow_x']], 'elbow_y': [graph['elbow_y']]}).to_csv(
+            osp.join(self.out_path, 'k_distance_elbow.csv'), index=False, float_format='%.17g')
+        return graph
 
     def train(self, train_data, valid_data, select_eps, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
         train_feat = train_data['hidden']
-        if select_eps == 'k_distance_graph':
-            logger.info('select_eps k_distance_graph: the {}-NN distance plot and its elbow are not produced'.format(self.min_sample - 1))
         dev = torch.device('cuda', torch.cuda.current_device())
         Xd = torch.as_tensor(train_feat, dtype=torch.float32, device=dev)
+        if select_eps == 'k_distance_graph':
+            self.k_distance_ = self.k_distance(Xd, overwrite)
         fits = dbscan_sweep(Xd, self.eps_range, self.min_sample)
         rows = []
         for eps, (labels, core) in zip(self.eps_range, fits):

@@ -613,6 +613,21 @@ int dic_dbscan_counts(const float* X, long ldx, const float* centre, int64_t N, 
 int dic_dbscan_components_pass(int64_t N, int D, float threshold, int eps_index, const int32_t* counts_e, int min_samples, const int32_t* band, int64_t n_band,
                                int32_t* labels, int32_t* border, int32_t* changed, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* k-th neighbour distances without the distance matrix (csrc/dic_knn.hip): p2_clustering_optK.py:110-112 takes
+ * NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X)[0][:, -1] for its k-distance graph; the same quantity is OPTICS' core distance.
+ * X, ldx, centre, N, D as for dic_dbscan_counts (D <= 256, D % 4 == 0, N < 2^30, 16-B aligned; centre (1, D) f32 = the mean of the points); 1 <= k <= N.
+ *   dic_knn_kth_distance: kth (N) f64 OVERWRITTEN = the k-th smallest of { |x_i - x_j| : j = 0..N-1 }, the self pair included (k = 1 gives 0): the f64 square
+ *       root of the f64 difference-form squared distance of the f32 coordinates, the value at the exact rank.  The split-bf16 tile products only narrow the
+ *       search (4 counting pair passes with per-row thresholds); the pairs they cannot rank -- the candidates -- are listed by one more pair pass, group of
+ *       rows by group of rows, and ranked exactly.  candidate_budget = the bytes of list storage inside the workspace (12 per candidate; <= 0: the default,
+ *       384 MiB; never more than 12 N^2), which sizes the groups and nothing else: the result does not depend on it.  stats (HOST, 5 int64, may be NULL):
+ *       counting passes, groups, the longest list, the candidates of all rows, the candidate_budget the longest list needs.  A row whose list alone exceeds
+ *       the budget returns DIC_ERR_WORKSPACE with stats filled (run again with candidate_budget >= stats[4]).  Reads list sizes back: synchronises `stream`.
+ *       Deterministic results. */
+size_t dic_knn_workspace(int64_t N, int D, int64_t candidate_budget);
+int dic_knn_kth_distance(const float* X, long ldx, const float* centre, int64_t N, int D, int64_t k, double* kth, int64_t candidate_budget, int64_t* stats,
+                         void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
