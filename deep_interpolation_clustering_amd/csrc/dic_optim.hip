@@ -40,7 +40,12 @@ __global__ __launch_bounds__(256) void adam_amsgrad_kernel(float* __restrict__ p
 }
 
 // clip_grad_norm_'s two scalars over the flat bucket: total = ||g||_2 (f64 accumulation of per-workgroup partials, fixed order),
-// coef = min(1, max_norm / (total + 1e-6)) (torch/nn/utils/clip_grad.py) -- two launches instead of norm + add + div + clamp
+// coef = clamp(max_norm / (total + 1e-6), max = 1) (torch/nn/utils/clip_grad.py) -- two launches instead of norm + add + div + clamp.
+// A non-finite gradient is handed on as torch hands it on: a NaN norm gives a NaN coefficient (not 1), the NaN coefficient multiplies
+// every gradient, and the Adam kernel above leaves every active parameter and its m, v NaN -- the step dies visibly.  (vmax keeps its
+// old value there: fmaxf drops the NaN where torch.maximum hands it on.  It is left so: the parameters are gone either way, and a select
+// in front of the maximum changes how the compiler contracts the m update, i.e. the bits of every healthy step.)
+// (tests/test_optim_oracle.py records torch's behaviour, tests/test_gpu_optim.py::test_nan_gradient_kills_the_step_as_torch_does holds this to it).
 __global__ __launch_bounds__(256) void grad_sqsum_kernel(const float* g, long n, double* partials) {
     __shared__ double red[4];
     float acc = 0.f;
@@ -56,7 +61,8 @@ __global__ __launch_bounds__(256) void grad_norm_finalize(const double* partials
     if (threadIdx.x == 0) {
         const float total = (float)sqrt(s);
         out2[0] = total;
-        out2[1] = fminf(1.0f, max_norm / (total + 1e-6f));
+        const float q = max_norm / (total + 1e-6f);
+        out2[1] = q > 1.0f ? 1.0f : q;          // clamp(max=1.0) keeps a NaN (fminf would turn it into 1)
     }
 }
 
@@ -111,12 +117,13 @@ int dic_grad_norm_clip(const float* g, int64_t n, float max_norm, float* out2, v
 int dic_accumulate_many(const float* const* src, float* const* dst, const int* n, int count, dic_stream_t stream) {
     DIC_REQUIRE(count >= 0, DIC_ERR_INVALID_ARG, "accumulate_many: negative count");
     DIC_REQUIRE(count == 0 || (src && dst && n), DIC_ERR_INVALID_ARG, "accumulate_many: NULL pointer");
+    for (int j = 0; j < count; ++j)          // (all entries before the first launch: a rejected call has added nothing)
+        DIC_REQUIRE(src[j] && dst[j] && n[j] > 0, DIC_ERR_INVALID_ARG, "accumulate_many: entry %d is empty", j);
     for (int base = 0; base < count; base += kAccumMax) {
         AccumMany a{};
         const int m = min(kAccumMax, count - base);
         int nmax = 0;
         for (int j = 0; j < m; ++j) {
-            DIC_REQUIRE(src[base + j] && dst[base + j] && n[base + j] > 0, DIC_ERR_INVALID_ARG, "accumulate_many: entry %d is empty", base + j);
             a.src[j] = src[base + j]; a.dst[j] = dst[base + j]; a.n[j] = n[base + j];
             nmax = max(nmax, n[base + j]);
         }

@@ -244,7 +244,7 @@ class FlatParams:
         # which parameters a backward pass actually reached: torch.optim skips parameters whose .grad is None (no weight decay,
         # no state), and with pre-allocated gradient views "None" has to be observed instead -- a hook per parameter flags it
         self._reached = [False] * len(self.params)
-        self._mask_key, self._mask = None, None
+        self._masks = {}          # reach pattern -> its byte mask, kept for the life of the bucket (active_mask)
         self._norm_ws = None
         self._split, self._split_index, self._tail_work = None, 0, None
         for i, p in enumerate(self.params):
@@ -257,13 +257,15 @@ class FlatParams:
 
     def active_mask(self):
         """Per-element byte mask of the parameters the last backward reached, or None when it reached all of them.  Cached per
-        reach pattern (it is a property of the loss configuration, constant from step to step)."""
+        reach pattern (it is a property of the loss configuration, constant from step to step), and a mask handed out once stays alive
+        and unchanged: a captured hipGraph of the step has its device pointer baked into the optimiser launch, so a later step under
+        another pattern must not free it (the patterns are as few as the loss configurations: 0.6 MB each)."""
         # (kernels that add a parameter gradient straight into its .grad view -- lstm._grad_sinks -- bypass autograd's
         # AccumulateGrad and therefore the hook: they leave the mark `_dic_grad_written` on the parameter instead)
         key = tuple(r or getattr(p, '_dic_grad_written', False) for r, p in zip(self._reached, self.params))
         if all(key) or not any(key):          # nothing recorded (e.g. a replayed hipGraph) counts as 'all', the common case
             return None
-        if key != self._mask_key:
+        if key not in self._masks:
             m = torch.zeros(self.flat.numel(), dtype=torch.uint8)
             o = 0
             for p, on in zip(self.params, key):
@@ -271,8 +273,8 @@ class FlatParams:
                 if on:
                     m[o:o + n] = 1
                 o += n
-            self._mask_key, self._mask = key, m.to(self.flat.device)
-        return self._mask
+            self._masks[key] = m.to(self.flat.device)
+        return self._masks[key]
 
     def _attach(self, copy=False):
         o = 0
