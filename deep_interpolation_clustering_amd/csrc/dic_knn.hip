@@ -26,6 +26,7 @@
 //     summed in a fixed order) and selects rank k - c_i by a radix select over the bit patterns of the (non-negative) doubles: the value AT the rank, ties or
 //     not.  The approximate products never decide the rank and never supply the value.
 // No workgroup waits for another inside a kernel; the only atomics are integer adds (counts, list cursors).  Two calls give the same bits.
+#include "dic_exactd2.h"
 #include "dic_pairtile.h"
 
 namespace dic {
@@ -306,8 +307,8 @@ __global__ __launch_bounds__(512, 1) void kn_gather_kernel(KnTileArgs a) {
     pt_pair_pass(a.p, epi);
 }
 
-// One workgroup per row of the group: the exact d^2 of every list entry (one wave per entry: lane l holds coordinates 4 l .. 4 l + 3, f64 difference form,
-// fixed summation order), then the value at rank k - c_i by a radix select over the doubles' bit patterns (non-negative: unsigned order = numeric order),
+// One workgroup per row of the group: the exact d^2 of every list entry (one wave per entry: dic_exactd2.h -- lane l holds coordinates 4 l .. 4 l + 3, f64
+// difference form, fixed summation order; dic_optics.hip computes its distances with the same function), then the value at rank k - c_i by a radix select over the doubles' bit patterns (non-negative: unsigned order = numeric order),
 // eight 8-bit digits from the top.  kth[i] = its square root.  plan->flag is set if a row's rank falls outside its list or a list slot holds no point (the
 // invariants say neither can happen).
 __global__ __launch_bounds__(256) void kn_exact_kernel(const float* X, long ldx, int d, int n, int r0, int k, const int32_t* cnt, const long long* off,
@@ -326,25 +327,14 @@ __global__ __launch_bounds__(256) void kn_exact_kernel(const float* X, long ldx,
         }
         return;
     }
-    const int col = 4 * lane;
-    pf32x4 xi = {0.f, 0.f, 0.f, 0.f};
-    if (col < d) xi = *reinterpret_cast<const pf32x4*>(X + (size_t)i * ldx + col);
+    const ed_f32x4 xi = exact_d2_load(X, ldx, (size_t)i, d);
     for (int e = w; e < len; e += 4) {
         int j = idx[o + e];
         if ((unsigned)j >= (unsigned)n) {          // a slot the gather pass did not fill (it fills every one): stay inside X and report
             if (lane == 0) plan->flag = 1;
             j = i;
         }
-        double s = 0.0;
-        if (col < d) {
-            const pf32x4 xj = *reinterpret_cast<const pf32x4*>(X + (size_t)j * ldx + col);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const double t = (double)xi[q] - (double)xj[q];
-                s = fma(t, t, s);
-            }
-        }
-        s = wave_sum(s);
+        const double s = exact_d2(xi, exact_d2_load(X, ldx, (size_t)j, d));
         if (lane == 0) d2[o + e] = s;
     }
     __syncthreads();

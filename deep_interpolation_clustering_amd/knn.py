@@ -4,7 +4,7 @@ Upstream: ``NearestNeighbors(n_neighbors=k, n_jobs=5).fit(X).kneighbors(X)[0][:,
 that curve from ``kneed.KneeLocator(point_num, sorted_dist, S=1.0, curve='convex', direction='increasing')``.  Here the distances come from
 csrc/dic_knn.hip: counting passes of the DBSCAN tile machine with per-row thresholds narrow every row's k-th distance to a short candidate list, and the
 value at the exact rank is taken from f64 difference-form distances of the candidates.  The convention is upstream's: the point itself is its own first
-neighbour (k = 1 gives 0, duplicates give zeros).  The same quantity is OPTICS' core distance (``core_distances``), the hook for an OPTICS on this machine.
+neighbour (k = 1 gives 0, duplicates give zeros).  The same quantity is OPTICS' core distance (``core_distances``): optics.py builds on it.
 """
 from __future__ import annotations
 
@@ -66,7 +66,7 @@ def kth_neighbor_distance(X, k, candidate_budget=None, stats=None):
 
 def core_distances(X, min_samples, candidate_budget=None, stats=None):
     """``sklearn.cluster.OPTICS(min_samples=min_samples, max_eps=inf).fit(X).core_distances_``: the distance to the min_samples-th neighbour, the point itself
-    counted -- ``kth_neighbor_distance(X, min_samples)``.  The first stone of an OPTICS on this machine."""
+    counted -- ``kth_neighbor_distance(X, min_samples)``.  optics.py rounds it to 15 decimals, as sklearn does, and walks the ordering from it."""
     return kth_neighbor_distance(X, min_samples, candidate_budget, stats)
 
 

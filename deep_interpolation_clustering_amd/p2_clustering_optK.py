@@ -11,8 +11,16 @@ Results/Pretrain/out_feat/<metric>_kmeans_aligned/plot/{elbow.csv, gap_sts_v1.cs
 ``--cluster_method dbscan`` (p2:82-85,90-168): DBSCAN for eps = 0.5, 1.0, .., 5.0 and min_samples = feat_dim + 1 on the GPU (dbscan.py: no N x N
 distance matrix), with the core / cluster / noise counts and both silhouettes per eps, written to <metric>_dbscan_aligned/plot/dbscan_eps.csv.  With
 --select_eps k_distance_graph (the default; p2:102-120) the feat_dim-NN distance curve of the training latents and its elbow -- the eps p4's --opt_eps is
-meant to be -- go to plot/k_distance.csv and plot/k_distance_elbow.csv (knn.py).  OPTICS, consensus and the seaborn plots of the upstream script are not
-provided.
+meant to be -- go to plot/k_distance.csv and plot/k_distance_elbow.csv (knn.py).
+
+``--cluster_method optics`` (p2:86-88,171-223): OPTICS with min_samples = feat_dim + 1 and the xi extraction (xi = .05, min_cluster_size = min_samples) on
+the GPU (optics.py: no N x N matrix, one launch per step of the main loop).  In place of the reachability plot its data go to
+<metric>_optics_aligned/plot/reachability_xi.csv (x, sample, dist, label: position in the ordering, point index, reachability, label -- every point, noise
+included) and the summary to plot/optics_xi.csv (min_samples, n_clusters, n_noise).  ONE DELIBERATE DEPARTURE: upstream calls
+``optics.fit(train_feat_dist)`` with the default metric (p2:196), which clusters the ROWS OF THE DISTANCE MATRIX as N-dimensional feature vectors; the
+commented-out ``optics.fit(train_feat)`` above it (p2:195) is the intent, and here OPTICS runs on the latents themselves.
+
+The consensus branch and the seaborn plots of the upstream script are not provided.
 """
 import argparse
 import os
@@ -30,6 +38,7 @@ from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
 from .kmeans import KMeans, seed_draw_count
 from .knn import k_distance_graph
+from .optics import OPTICS
 from .utils import logger, print_dict_byline
 
 np.random.seed(123)        # p2_clustering_optK.py:23
@@ -356,6 +365,52 @@ class Dbscan(object):
         return df
 
 
+class Optics(object):
+    """Optics.train (p2:171-223): one OPTICS fit of the training latents -- ``cluster_method`` 'xi' (xi = .05, min_cluster_size = min_samples) or 'dbscan'
+    (eps = max_eps = inf) -- logged as upstream logs it; returns (and writes to plot/optics_<cluster_method>.csv) the one-row summary, and writes the data
+    of upstream's reachability plot to plot/reachability_<cluster_method>.csv, every point included.  An existing reachability file is left alone unless
+    ``overwrite`` is set, as upstream leaves its plot; the summary on disk is returned then.  The fit runs on the latents, not on the rows of their distance
+    matrix (module docstring).  ``fit_`` keeps the fitted ``OPTICS`` of the last run that computed one."""
+    COLUMNS = ['min_samples', 'n_clusters', 'n_noise']
+
+    def __init__(self, min_samples, cluster_method, out_path):
+        if cluster_method not in ('xi', 'dbscan'):
+            raise ValueError("cluster_method must be 'xi' or 'dbscan', got %r" % (cluster_method,))
+        self.min_sample = min_samples
+        self.cluster_method = cluster_method
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.fit_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fit_ = None
+        plot_csv = osp.join(self.out_path, 'reachability_{}.csv'.format(self.cluster_method))
+        summary_csv = osp.join(self.out_path, 'optics_{}.csv'.format(self.cluster_method))
+        if osp.exists(plot_csv) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(plot_csv))
+            return pd.read_csv(summary_csv) if osp.exists(summary_csv) else None
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        if self.cluster_method == 'xi':
+            optics = OPTICS(min_samples=self.min_sample, cluster_method='xi', xi=.05, min_cluster_size=self.min_sample)
+        else:
+            optics = OPTICS(min_samples=self.min_sample, cluster_method='dbscan')
+        optics.fit(Xd)
+        labels = optics.labels_
+        n_clusters_ = len(set(labels.tolist())) - (1 if -1 in labels else 0)
+        n_noise_ = int(np.sum(labels == -1))
+        logger.info('OPTICS with cluster_method: {}, n_clusters: {}, n_noise: {}'.format(self.cluster_method, n_clusters_, n_noise_))
+        order = optics.ordering_
+        pd.DataFrame({'x': np.arange(len(order)), 'sample': order, 'dist': optics.reachability_[order], 'label': labels[order]}).to_csv(
+            plot_csv, index=False, float_format='%.17g')
+        df = pd.DataFrame([[int(self.min_sample), n_clusters_, n_noise_]], columns=self.COLUMNS)
+        df.to_csv(summary_csv, index=False)
+        logger.info('Saved for {}!.'.format(plot_csv))
+        self.fit_ = optics
+        return df
+
+
 class Cluster(object):
     def __init__(self, args):
         self.args = args
@@ -383,8 +438,13 @@ class Cluster(object):
                     db = Dbscan(eps_range=eps_range, min_samples=self.feat_dim + 1, out_path=self.out_path)
                     results[metric] = db.train(self.train_data, self.valid_data, self.args.select_eps)
                 continue
+            if self.args.cluster_method == 'optics':
+                if dist.rank() == 0:            # one fit, on rank 0; the other ranks wait at main's barrier
+                    op = Optics(min_samples=self.feat_dim + 1, cluster_method='xi', out_path=self.out_path)
+                    results[metric] = op.train(self.train_data, self.valid_data)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans and dbscan are on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans, dbscan and optics are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

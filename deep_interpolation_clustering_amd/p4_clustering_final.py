@@ -6,7 +6,8 @@ systolic pressure so ids are comparable across runs (generate_align_map, p4:63-9
 writes .../<metric>_<method>_aligned/<cohort>_<k>.npy with an added ``cluster_id``.
 ``dbscan`` (p4:181-236): a DBSCAN(opt_eps, min_samples = feat_dim) fit per cohort on the GPU (dbscan.py), training clusters re-numbered by
 sbp (generate_align_map), validation / test clusters mapped onto the nearest training centre (align_labels_with_center); writes
-<cohort>_eps-<opt_eps>.npy.  The consensus branch of the upstream script is not provided.
+<cohort>_eps-<opt_eps>.npy.  ``optics`` is accepted by the parser but does nothing upstream (its branch is ``pass``, p4:238-239), so there is nothing to
+provide here: it raises, as does the consensus branch, which is not provided.  (p2's optics branch exists: optics.py.)
 """
 import argparse
 import copy
@@ -160,7 +161,8 @@ class Cluster(object):
             elif self.args.cluster_method == 'dbscan':
                 self._dbscan(cohorts, overwrite)
             else:
-                raise NotImplementedError("only 'kmeans', 'dl' and 'dbscan' are on the accelerated path")
+                raise NotImplementedError("only 'kmeans', 'dl' and 'dbscan' are on the accelerated path: upstream's 'optics' branch of p4 is an empty `pass` "
+                                          "(p2 has the OPTICS fit), and 'consensus' is not provided")
 
 
 def main(args):

@@ -614,7 +614,7 @@ int dic_dbscan_components_pass(int64_t N, int D, float threshold, int eps_index,
                                int32_t* labels, int32_t* border, int32_t* changed, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
 /* k-th neighbour distances without the distance matrix (csrc/dic_knn.hip): p2_clustering_optK.py:110-112 takes
- * NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X)[0][:, -1] for its k-distance graph; the same quantity is OPTICS' core distance.
+ * NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X)[0][:, -1] for its k-distance graph; the same quantity is OPTICS' core distance (dic_optics_order below takes it).
  * X, ldx, centre, N, D as for dic_dbscan_counts (D <= 256, D % 4 == 0, N < 2^30, 16-B aligned; centre (1, D) f32 = the mean of the points); 1 <= k <= N.
  *   dic_knn_kth_distance: kth (N) f64 OVERWRITTEN = the k-th smallest of { |x_i - x_j| : j = 0..N-1 }, the self pair included (k = 1 gives 0): the f64 square
  *       root of the f64 difference-form squared distance of the f32 coordinates, the value at the exact rank.  The split-bf16 tile products only narrow the
@@ -627,6 +627,22 @@ int dic_dbscan_components_pass(int64_t N, int D, float threshold, int eps_index,
 size_t dic_knn_workspace(int64_t N, int D, int64_t candidate_budget);
 int dic_knn_kth_distance(const float* X, long ldx, const float* centre, int64_t N, int D, int64_t k, double* kth, int64_t candidate_budget, int64_t* stats,
                          void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
+/* OPTICS' ordering without the distance matrix (csrc/dic_optics.hip): p2_clustering_optK.py:86-88,171-223 fits sklearn.cluster.OPTICS; this is its main loop
+ * in the self-consistent form sklearn has with metric='precomputed' on the f64 difference-form distances d of the f32 points.  X, ldx, N, D as for
+ * dic_knn_kth_distance (D <= 256, D % 4 == 0, N < 2^30, X and the workspace 16-B aligned).  core (N) f64, DEVICE, in: the core distances, already set to inf
+ * above max_eps and rounded as np.around(., 15) rounds (around15(v) = rint(v * 1e15) / 1e15) -- dic_knn_kth_distance(k = min_samples) supplies the values,
+ * and its distances are bit for bit this file's (csrc/dic_exactd2.h), which the tie-breaking by index relies on.  max_eps >= 0, inf allowed.
+ *   dic_optics_order: ordering (N) int32, reachability (N) f64, predecessor (N) int32, all OVERWRITTEN.  reachability = inf, predecessor = -1, nothing
+ *       processed; N times: p = the unprocessed point of smallest reachability (ties, inf included: the smallest index) is appended to ordering; if core[p]
+ *       is finite, every unprocessed q with d(p, q) <= max_eps takes r = around15(max(d(p, q), core[p])) and predecessor p where r < reachability[q].
+ *       One launch per step, a row pass over X that also finds the next p (the workgroup arriving last reduces the others' minima); the N - 1 launches are
+ *       enqueued on `stream` without synchronising and the call returns while they run: the results are complete when the stream has drained.  No launch
+ *       waits for another workgroup.  The workspace (dic_optics_workspace(N, D) bytes, O(N)) holds the processed flags, the workgroup minima, the current
+ *       point and the arrival counter.  Deterministic results. */
+size_t dic_optics_workspace(int64_t N, int D);
+int dic_optics_order(const float* X, long ldx, int64_t N, int D, const double* core, double max_eps, int32_t* ordering, double* reachability,
+                     int32_t* predecessor, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
 #ifdef __cplusplus
 }
