@@ -20,7 +20,14 @@ included) and the summary to plot/optics_xi.csv (min_samples, n_clusters, n_nois
 ``optics.fit(train_feat_dist)`` with the default metric (p2:196), which clusters the ROWS OF THE DISTANCE MATRIX as N-dimensional feature vectors; the
 commented-out ``optics.fit(train_feat)`` above it (p2:195) is the intent, and here OPTICS runs on the latents themselves.
 
-The consensus branch and the seaborn plots of the upstream script are not provided.
+``--cluster_method consensus``: upstream has no such fit -- its p4 reads out_feat/raw_consensus_result/<cohort>_consensus.csv (columns k2, k3, ..), labels
+"generated outside" (p4_clustering_final.py:241-287).  Here they are generated: consensus clustering with a k-means base clusterer for K = 2..k_max
+(consensus.py: --consensus_reps resamples of --consensus_p_item of the points, the pair consensus, its CDF and the average-linkage cut on the GPU) on the
+training latents, whose CDFs go to <metric>_consensus_aligned/plot/consensus_cdf.csv (k, c, cdf) and the areas under them to plot/consensus_area.csv (k,
+area, delta_area); the 1-based labels of the training and of the validation cohort, each clustered on its own as the outside step did, go to
+out_feat/raw_consensus_result/{training,validation}_consensus.csv in the format p4 reads.
+
+The seaborn plots of the upstream script are not provided.
 """
 import argparse
 import os
@@ -33,6 +40,7 @@ import pandas as pd
 import torch
 
 from . import cluster_stats, dist
+from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
 from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
@@ -55,6 +63,8 @@ def get_arguments(argv=None):
     p.add_argument('--restore_metric', default=['ae_mse', 'loss'])
     p.add_argument('--opt_eps', type=float, default=1.9)
     p.add_argument('--internal_metrics', default=['Sihouette', 'Davies-Bouldin_Index', 'Calinski-Harabasz'])
+    p.add_argument('--consensus_reps', type=int, default=100, help='(extra) resamples of the consensus clustering')
+    p.add_argument('--consensus_p_item', type=float, default=0.8, help='(extra) fraction of the points in a resample')
     p.add_argument('--metric_sample', type=int, default=0, help='(extra) subsample size for the O(N^2) validity indices; 0 = all')
     return p.parse_args(argv)
 
@@ -411,6 +421,52 @@ class Optics(object):
         return df
 
 
+class Consensus(object):
+    """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
+    training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
+    labels of either cohort to ``raw_path``/<cohort>_consensus.csv (columns k2..k<k_max>), the file p4's consensus branch reads.  A cohort whose files exist
+    is left alone unless ``overwrite`` is set.  Returns the area table (read back from disk when it was left alone); ``fits_`` keeps the fits of this run."""
+
+    def __init__(self, k_max, out_path, raw_path, reps=100, p_item=0.8, n_init=1, seed=0):
+        self.ks = list(range(2, k_max + 1))
+        self.reps, self.p_item, self.n_init, self.seed = reps, p_item, n_init, seed
+        self.out_path = osp.join(out_path, 'plot')
+        self.raw_path = raw_path
+        os.makedirs(self.out_path, exist_ok=True)
+        os.makedirs(self.raw_path, exist_ok=True)
+        self.fits_ = {}
+
+    def _fit(self, cohort, feat):
+        logger.info('Consensus clustering of the {} cohort: K = {}..{}, {} resamples'.format(cohort, self.ks[0], self.ks[-1], self.reps))
+        dev = torch.device('cuda', torch.cuda.current_device())
+        cc = ConsensusKMeans(self.ks, reps=self.reps, p_item=self.p_item, n_init=self.n_init, seed=self.seed)
+        cc.fit(torch.as_tensor(feat, dtype=torch.float32, device=dev))
+        self.fits_[cohort] = cc
+        return cc
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fits_ = {}
+        cdf_csv, area_csv = osp.join(self.out_path, 'consensus_cdf.csv'), osp.join(self.out_path, 'consensus_area.csv')
+        for cohort, data in (('training', train_data), ('validation', valid_data)):
+            raw_csv = osp.join(self.raw_path, '{}_consensus.csv'.format(cohort))
+            wanted = [raw_csv] + ([cdf_csv, area_csv] if cohort == 'training' else [])
+            if all(osp.exists(f) for f in wanted) and not overwrite:
+                logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(raw_csv))
+                continue
+            cc = self._fit(cohort, data['hidden'])
+            pd.DataFrame({'k{}'.format(k): cc.labels_[k] for k in self.ks}).to_csv(raw_csv, index=False)
+            if cohort == 'training':
+                grid = np.arange(BINS + 1) / BINS
+                pd.concat([pd.DataFrame({'k': k, 'c': grid, 'cdf': cc.cdf_[k]}) for k in self.ks]).to_csv(cdf_csv, index=False, float_format='%.17g')
+                pd.DataFrame({'k': self.ks, 'area': [cc.area_[k] for k in self.ks], 'delta_area': [cc.delta_area_[k] for k in self.ks]}).to_csv(
+                    area_csv, index=False, float_format='%.17g')
+                for k in self.ks:
+                    logger.info('k: {}, area: {:.5f}, delta_area: {:.5f}'.format(k, cc.area_[k], cc.delta_area_[k]))
+            logger.info('Saved for {}!.'.format(raw_csv))
+        return pd.read_csv(area_csv, float_precision='round_trip')          # (%.17g: exact)
+
+
 class Cluster(object):
     def __init__(self, args):
         self.args = args
@@ -443,8 +499,14 @@ class Cluster(object):
                     op = Optics(min_samples=self.feat_dim + 1, cluster_method='xi', out_path=self.out_path)
                     results[metric] = op.train(self.train_data, self.valid_data)
                 continue
+            if self.args.cluster_method == 'consensus':
+                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
+                    co = Consensus(self.args.k_max, self.out_path, osp.join(self.exp_path, 'out_feat', 'raw_consensus_result'),
+                                   reps=self.args.consensus_reps, p_item=self.args.consensus_p_item)
+                    results[metric] = co.train(self.train_data, self.valid_data)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans, dbscan and optics are on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics and consensus are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

@@ -7,7 +7,11 @@ writes .../<metric>_<method>_aligned/<cohort>_<k>.npy with an added ``cluster_id
 ``dbscan`` (p4:181-236): a DBSCAN(opt_eps, min_samples = feat_dim) fit per cohort on the GPU (dbscan.py), training clusters re-numbered by
 sbp (generate_align_map), validation / test clusters mapped onto the nearest training centre (align_labels_with_center); writes
 <cohort>_eps-<opt_eps>.npy.  ``optics`` is accepted by the parser but does nothing upstream (its branch is ``pass``, p4:238-239), so there is nothing to
-provide here: it raises, as does the consensus branch, which is not provided.  (p2's optics branch exists: optics.py.)
+provide here: it raises.  (p2's optics branch exists: optics.py.)
+``consensus`` (p4:241-287): reads the raw consensus labels of out_feat/raw_consensus_result/<cohort>_consensus.csv (column k<num_clusters>, 0- or 1-based),
+re-numbers the training clusters by sbp (generate_align_map) and applies that map to the training and the validation cohort (upstream leaves the test cohort
+out); writes <cohort>_<k>.npy.  Upstream's csv files were "generated outside"; a missing one is first computed here by consensus clustering of that cohort's
+latents on the GPU (consensus.py) and written.
 """
 import argparse
 import copy
@@ -15,6 +19,7 @@ import os
 import os.path as osp
 
 import numpy as np
+import pandas as pd
 
 from . import cluster_stats
 from .dbscan import DBSCAN
@@ -121,6 +126,51 @@ class Cluster(object):
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
             np.save(f, data)
 
+    def _raw_consensus(self, cohort, data):
+        """The raw consensus labels of a cohort for k = num_clusters, 0-based as generate_align_map wants them (p4:247-253): column k<num_clusters> of
+        raw_consensus_result/<cohort>_consensus.csv, computed and written first where the file is missing."""
+        col = 'k{}'.format(self.args.num_clusters)
+        raw_dir = osp.join(self.exp_path, 'out_feat', 'raw_consensus_result')
+        f = osp.join(raw_dir, '{}_consensus.csv'.format(cohort))
+        if not osp.exists(f):
+            from .consensus import ConsensusKMeans          # (the GPU is touched only when a file has to be made)
+            logger.info('NEW consensus clustering for {}: {}'.format(cohort, f))
+            os.makedirs(raw_dir, exist_ok=True)
+            cc = ConsensusKMeans([self.args.num_clusters]).fit(np.asarray(data['hidden'], dtype=np.float32))
+            pd.DataFrame({col: cc.labels_[self.args.num_clusters]}).to_csv(f, index=False)
+        raw_label = pd.read_csv(f)[col].values
+        if not any(raw_label == 0):
+            raw_label = raw_label - 1          # adjust label starting from 0, to be comparable to generate_align_map
+        return raw_label
+
+    @staticmethod
+    def renumber_consensus(raw_label, align_map):
+        """p4:273-279: the 0-based raw labels through ``align_map`` {old id: new id}.  Mapped ids are parked as negatives (and new id 0 under a spare tag)
+        so that an id already mapped is not mapped again."""
+        raw_label = np.array(raw_label)
+        tag = max(align_map.keys()) + 10
+        for org_id, new_id in align_map.items():
+            if new_id == 0:          # label the 0 as None
+                raw_label[raw_label == org_id] = tag
+            raw_label[raw_label == org_id] = -new_id
+        raw_label[raw_label == tag] = 0
+        return abs(raw_label)
+
+    def _consensus(self, overwrite):
+        opt_k = self.args.num_clusters
+        logger.info('==> Generate the consensus clustering results with opt-k: {}'.format(opt_k))
+        train_raw_label = self._raw_consensus('training', self.train_data)
+        align_map, _, _ = self.generate_align_map(train_raw_label, self.train_data['ob'], self.train_data['padding_mask'])
+        for cohort, data in zip(COHORTS, [self.train_data, self.valid_data]):
+            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, opt_k))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            data['cluster_id'] = self.renumber_consensus(self._raw_consensus(cohort, data), align_map)
+            del data['ob'], data['padding_mask']
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+            np.save(f, data)
+
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         for metric in self.args.restore_metric:
@@ -160,9 +210,11 @@ class Cluster(object):
                     logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
             elif self.args.cluster_method == 'dbscan':
                 self._dbscan(cohorts, overwrite)
+            elif self.args.cluster_method == 'consensus':
+                self._consensus(overwrite)
             else:
-                raise NotImplementedError("only 'kmeans', 'dl' and 'dbscan' are on the accelerated path: upstream's 'optics' branch of p4 is an empty `pass` "
-                                          "(p2 has the OPTICS fit), and 'consensus' is not provided")
+                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan' and 'consensus' are on the accelerated path: upstream's 'optics' branch of p4 is an "
+                                          "empty `pass` (p2 has the OPTICS fit)")
 
 
 def main(args):

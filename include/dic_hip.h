@@ -644,6 +644,36 @@ size_t dic_optics_workspace(int64_t N, int D);
 int dic_optics_order(const float* X, long ldx, int64_t N, int D, const double* core, double max_eps, int32_t* ordering, double* reachability,
                      int32_t* predecessor, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* Consensus clustering from a label matrix and the average-linkage agglomeration of its consensus distance (csrc/dic_consensus.hip): the p2 / p4
+ * `--cluster_method consensus` branches (p4_clustering_final.py:241-287 reads labels "generated outside": Monti-style consensus clustering with a k-means
+ * base clusterer, ConsensusClusterPlus' conventions).  L (N, ldl) uint8, DEVICE, 16-B aligned: L[i, h] for h < H is the label 0..K-1 (K <= 254) of point i in
+ * resample h, or 0xFF where resample h left the point out; ldl % 16 == 0 and the columns H..ldl-1 hold 0xFF.  2 <= N < 2^30, 1 <= H <= 65535.  For a pair, in
+ * integers: both = #{h: L_ih != FF and L_jh != FF}, agree = #{h: L_ih == L_jh != FF}; consensus M(i, j) = agree / both, 0 when both == 0.
+ *   dic_consensus_pairs: one tiled pass over the pairs for each of the outputs asked for (NULL: skipped; at least one):
+ *       hist (DIC_CONSENSUS_BINS + 1) u64 OVERWRITTEN: over the unordered pairs i < j, the exact count of t = ceil(B agree / both) in integer arithmetic,
+ *           (B agree + both - 1) / both, t = 0 when both == 0 (B = DIC_CONSENSUS_BINS).
+ *       D (N, N) f64 OVERWRITTEN: 1.0 - (double)agree / (double)both, one f64 division and one subtraction; 1.0 when both == 0; 0 on the diagonal; (i, j) and
+ *           (j, i) are stored from one register: exactly symmetric.
+ *       rowsum (N, K) f64 OVERWRITTEN = sum over j != i with y[j] == c of M(i, j), each term (double)agree / (double)both, summed in f64 in a fixed order (the
+ *           rows are sorted by cluster first and every row has one owner; no floating-point atomics): needs y (N) int32, DEVICE, 1 <= K <= 254 and the
+ *           workspace (dic_consensus_pairs_workspace(N, H, K) bytes; K = 0: no rowsum, no workspace needed).  A y[j] outside 0..K-1 belongs to no cluster.
+ *       Every output has the same bits whichever others are asked for, and from call to call.  Enqueued on `stream` without synchronising.
+ *   dic_linkage_average: scipy.cluster.hierarchy.linkage(., 'average') on the SQUARE symmetric matrix D (N, N) f64, DEVICE, which is DESTROYED: the
+ *       nearest-neighbour chain with scipy's tie-breaking -- size[i] = 1, chain empty; N - 1 times: an empty chain becomes [smallest live i]; repeat x =
+ *       chain[-1], y = the live i != x of smallest (D[x, i], i) except that chain[-2] wins a tie with that minimum, until y == chain[-2], else append y; pop
+ *       both, (x, y) = (min, max), record, size[x] = 0, size[y] = nx + ny, D[i, y] = D[y, i] = (nx D[i, x] + ny D[i, y]) / (nx + ny) for every live i != y, each
+ *       operation correctly rounded in f64 and none contracted.  records (N - 1, 4) f64 OVERWRITTEN: (x, y, height, nx + ny) per merge in the order the
+ *       merges happen: NOT sorted by height and not relabelled (consensus.average_linkage does both on the host).  One launch of one workgroup per repeat of
+ *       the inner loop, 3 (N - 1) launches in all, enqueued without synchronising; size, chain and the counters live in the workspace
+ *       (dic_linkage_average_workspace(N) bytes, O(N); its last 256 B begin with three int32: chain length, merges done, launches that pushed or merged);
+ *       no workgroup waits for another.  8 N^2 bytes of D: the caller checks that they fit.  Deterministic. */
+#define DIC_CONSENSUS_BINS 100
+size_t dic_consensus_pairs_workspace(int64_t N, int H, int K);
+int dic_consensus_pairs(const unsigned char* L, long ldl, int64_t N, int H, const int32_t* y, int K, unsigned long long* hist, double* rowsum, double* D,
+                        void* workspace, size_t workspace_bytes, dic_stream_t stream);
+size_t dic_linkage_average_workspace(int64_t N);
+int dic_linkage_average(double* D, int64_t N, double* records, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
