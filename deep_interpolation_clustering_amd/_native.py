@@ -138,6 +138,8 @@ SIGNATURES = {
     'dic_knn_kth_distance': (_i, [_p, C.c_long, _p, C.c_int64, _i, C.c_int64, _p, C.c_int64, _p, _p, _sz, _p]),
     'dic_optics_workspace': (_sz, [C.c_int64, _i]),
     'dic_optics_order': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_double, _p, _p, _p, _p, _sz, _p]),
+    'dic_hdbscan_workspace': (_sz, [C.c_int64, _i]),
+    'dic_hdbscan_mst': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, _p, _p, _p, _sz, _p]),
     'dic_consensus_pairs_workspace': (_sz, [C.c_int64, _i, _i]),
     'dic_consensus_pairs': (_i, [_p, C.c_long, C.c_int64, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
     'dic_linkage_average_workspace': (_sz, [C.c_int64]),

@@ -27,6 +27,12 @@ training latents, whose CDFs go to <metric>_consensus_aligned/plot/consensus_cdf
 area, delta_area); the 1-based labels of the training and of the validation cohort, each clustered on its own as the outside step did, go to
 out_feat/raw_consensus_result/{training,validation}_consensus.csv in the format p4 reads.
 
+``--cluster_method hdbscan`` (no upstream counterpart): HDBSCAN with min_samples = feat_dim + 1 on the training latents on the GPU (hdbscan.py: no N x N
+matrix, one launch per step of Prim's walk over the mutual-reachability graph), extracted for every --hdbscan_min_cluster_size (default feat_dim + 1; the
+tree does not depend on it).  The walk goes to <metric>_hdbscan_aligned/plot/hdbscan_mst.csv (x, sample, source, dist: position in the walk, point index,
+its neighbour in the tree, the weight it joined at), the per-size table to plot/hdbscan_sizes.csv (min_cluster_size, n_clusters, n_noise, silhouette,
+denoise_silhouette) and the labels to plot/hdbscan_labels.csv, one column mcs<size> per size.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -42,6 +48,7 @@ import torch
 from . import cluster_stats, dist
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
+from .hdbscan import hdbscan_sizes
 from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
 from .kmeans import KMeans, seed_draw_count
@@ -54,7 +61,7 @@ np.random.seed(123)        # p2_clustering_optK.py:23
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan'])
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -65,6 +72,8 @@ def get_arguments(argv=None):
     p.add_argument('--internal_metrics', default=['Sihouette', 'Davies-Bouldin_Index', 'Calinski-Harabasz'])
     p.add_argument('--consensus_reps', type=int, default=100, help='(extra) resamples of the consensus clustering')
     p.add_argument('--consensus_p_item', type=float, default=0.8, help='(extra) fraction of the points in a resample')
+    p.add_argument('--hdbscan_min_cluster_size', type=int, nargs='+', default=None,
+                   help='(extra) min_cluster_size values of --cluster_method hdbscan; default feat_dim + 1')
     p.add_argument('--metric_sample', type=int, default=0, help='(extra) subsample size for the O(N^2) validity indices; 0 = all')
     return p.parse_args(argv)
 
@@ -421,6 +430,61 @@ class Optics(object):
         return df
 
 
+class Hdbscan(object):
+    """One HDBSCAN tree of the training latents (min_samples as given) and one extraction per ``min_cluster_sizes`` entry, logged as Dbscan.train logs its
+    fits.  Writes plot/hdbscan_mst.csv (x, sample, source, dist: every step of Prim's walk, %.17g), plot/hdbscan_sizes.csv (``COLUMNS``; the silhouettes as
+    the DBSCAN branch computes them, empty below 2 clusters) and plot/hdbscan_labels.csv (one column mcs<size> per size), and returns the per-size table.
+    Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.  ``fit_`` keeps the fitted ``HDBSCAN`` of the last run
+    that computed one, ``labels_`` its labels per size."""
+    COLUMNS = ['min_cluster_size', 'n_clusters', 'n_noise', 'silhouette', 'denoise_silhouette']
+    FILES = ('hdbscan_mst.csv', 'hdbscan_sizes.csv', 'hdbscan_labels.csv')
+
+    def __init__(self, min_samples, min_cluster_sizes, out_path):
+        self.min_sample = min_samples
+        self.min_cluster_sizes = [int(m) for m in min_cluster_sizes]
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.fit_ = self.labels_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fit_ = self.labels_ = None
+        mst_csv, sizes_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (mst_csv, sizes_csv, labels_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(mst_csv))
+            return pd.read_csv(sizes_csv)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        fit, found = hdbscan_sizes(Xd, self.min_sample, self.min_cluster_sizes)
+        order = fit.ordering_
+        pd.DataFrame({'x': np.arange(len(order)), 'sample': order, 'source': fit.predecessor_[order], 'dist': fit.reachability_[order]}).to_csv(
+            mst_csv, index=False, float_format='%.17g')
+        rows = []
+        for mcs in self.min_cluster_sizes:
+            labels = found[mcs][0]
+            n_clusters_ = len(set(labels.tolist())) - (1 if -1 in labels else 0)
+            n_noise_ = int(np.sum(labels == -1))
+            logger.info('\nRunning min_cluster_size: {}'.format(mcs))
+            logger.info('Estimated number of clusters: %d' % n_clusters_)
+            logger.info('Estimated number of noise points: %d' % n_noise_)
+            sil = sil_dn = float('nan')
+            if n_clusters_ == 1:
+                logger.info('Skip the Silhouette Coefficient calculation.')
+            elif n_clusters_ > 1:
+                keep = labels != -1
+                sil = cluster_stats.silhouette_score(Xd, labels)
+                sil_dn = cluster_stats.silhouette_score(Xd[torch.as_tensor(keep, device=dev)], labels[keep])
+                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(labels), sil))
+                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(int(keep.sum()), sil_dn))
+            rows.append([mcs, n_clusters_, n_noise_, sil, sil_dn])
+        df = pd.DataFrame(rows, columns=self.COLUMNS)
+        df.to_csv(sizes_csv, index=False)
+        pd.DataFrame({'mcs{}'.format(m): found[m][0] for m in self.min_cluster_sizes}).to_csv(labels_csv, index=False)
+        logger.info('Saved for {}!.'.format(mst_csv))
+        self.fit_, self.labels_ = fit, {m: found[m][0] for m in self.min_cluster_sizes}
+        return df
+
+
 class Consensus(object):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
@@ -505,8 +569,14 @@ class Cluster(object):
                                    reps=self.args.consensus_reps, p_item=self.args.consensus_p_item)
                     results[metric] = co.train(self.train_data, self.valid_data)
                 continue
+            if self.args.cluster_method == 'hdbscan':
+                if dist.rank() == 0:            # one tree, on rank 0; the other ranks wait at main's barrier
+                    sizes = self.args.hdbscan_min_cluster_size or [self.feat_dim + 1]
+                    hd = Hdbscan(min_samples=self.feat_dim + 1, min_cluster_sizes=sizes, out_path=self.out_path)
+                    results[metric] = hd.train(self.train_data, self.valid_data)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics and consensus are on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus and hdbscan are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

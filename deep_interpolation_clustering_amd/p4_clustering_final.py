@@ -8,6 +8,9 @@ writes .../<metric>_<method>_aligned/<cohort>_<k>.npy with an added ``cluster_id
 sbp (generate_align_map), validation / test clusters mapped onto the nearest training centre (align_labels_with_center); writes
 <cohort>_eps-<opt_eps>.npy.  ``optics`` is accepted by the parser but does nothing upstream (its branch is ``pass``, p4:238-239), so there is nothing to
 provide here: it raises.  (p2's optics branch exists: optics.py.)
+``hdbscan`` (no upstream counterpart; the dbscan branch without its eps): an HDBSCAN(min_cluster_size = --hdbscan_min_cluster_size, default feat_dim + 1,
+min_samples = feat_dim + 1) fit per cohort on the GPU (hdbscan.py), training clusters re-numbered by sbp, validation / test clusters mapped onto the nearest
+training centre, exactly as the dbscan branch does it; writes <cohort>_mcs-<min_cluster_size>.npy.
 ``consensus`` (p4:241-287): reads the raw consensus labels of out_feat/raw_consensus_result/<cohort>_consensus.csv (column k<num_clusters>, 0- or 1-based),
 re-numbers the training clusters by sbp (generate_align_map) and applies that map to the training and the validation cohort (upstream leaves the test cohort
 out); writes <cohort>_<k>.npy.  Upstream's csv files were "generated outside"; a missing one is first computed here by consensus clustering of that cohort's
@@ -23,6 +26,7 @@ import pandas as pd
 
 from . import cluster_stats
 from .dbscan import DBSCAN
+from .hdbscan import HDBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
 from .utils import logger, print_dict_byline
@@ -32,10 +36,11 @@ np.random.seed(123)        # p4_clustering_final.py:24
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
+    p.add_argument('--hdbscan_min_cluster_size', type=int, default=None, help='(extra) min_cluster_size of --cluster_method hdbscan; default feat_dim + 1')
     p.add_argument('--dl_cluster_label_type', default='pred', choices=['label', 'pred'])
     return p.parse_args(argv)
 
@@ -117,6 +122,41 @@ class Cluster(object):
             logger.info('Estimated number of noise points: %d' % n_noise_)
             if n_clusters_ == 0:
                 continue                      # (upstream writes nothing for this cohort either)
+            elif n_clusters_ == 1:
+                logger.info('Skip the Silhouette Coefficient calculation.')
+            else:
+                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(aligned_label), cluster_stats.silhouette_score(feat, aligned_label)))
+                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(
+                    int(keep.sum()), cluster_stats.silhouette_score(feat[keep], aligned_label[keep])))
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+            np.save(f, data)
+
+    def _hdbscan(self, cohorts, overwrite):
+        min_samples = self.feat_dim + 1
+        mcs = self.args.hdbscan_min_cluster_size if self.args.hdbscan_min_cluster_size is not None else self.feat_dim + 1
+        logger.info('==> Generate the HDBSCAN results with min_cluster_size: {}, min_samples: {}'.format(mcs, min_samples))
+        train_feat_centers = None
+        for cohort, data in cohorts:
+            f = osp.join(self.out_path, '{}_mcs-{}.npy'.format(cohort, mcs))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            logger.info('NEW HDBSCAN model for {}'.format(cohort))
+            feat = data['hidden']
+            raw_label = HDBSCAN(min_cluster_size=mcs, min_samples=min_samples).fit(feat).labels_
+            if cohort == 'training':
+                _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
+            else:
+                aligned_label = self.align_labels_with_center(feat, raw_label, train_feat_centers)
+            data['cluster_id'] = aligned_label
+            del data['ob'], data['padding_mask']
+            n_clusters_ = len(set(aligned_label)) - (1 if -1 in aligned_label else 0)
+            n_noise_ = int(np.sum(aligned_label == -1))
+            keep = aligned_label != -1
+            logger.info('Estimated number of clusters: %d' % n_clusters_)
+            logger.info('Estimated number of noise points: %d' % n_noise_)
+            if n_clusters_ == 0:
+                continue                      # (as the dbscan branch: nothing is written for this cohort)
             elif n_clusters_ == 1:
                 logger.info('Skip the Silhouette Coefficient calculation.')
             else:
@@ -212,8 +252,10 @@ class Cluster(object):
                 self._dbscan(cohorts, overwrite)
             elif self.args.cluster_method == 'consensus':
                 self._consensus(overwrite)
+            elif self.args.cluster_method == 'hdbscan':
+                self._hdbscan(cohorts, overwrite)
             else:
-                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan' and 'consensus' are on the accelerated path: upstream's 'optics' branch of p4 is an "
+                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus' and 'hdbscan' are on the accelerated path: upstream's 'optics' branch of p4 is an "
                                           "empty `pass` (p2 has the OPTICS fit)")
 
 

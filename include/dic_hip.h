@@ -644,6 +644,24 @@ size_t dic_optics_workspace(int64_t N, int D);
 int dic_optics_order(const float* X, long ldx, int64_t N, int D, const double* core, double max_eps, int32_t* ordering, double* reachability,
                      int32_t* predecessor, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* HDBSCAN's minimum spanning tree without the distance matrix (csrc/dic_hdbscan.hip): Prim's walk over the mutual-reachability graph
+ * mr(p, q) = max(core[p], core[q], d(p, q)) as sklearn.cluster.HDBSCAN(metric='precomputed', algorithm='brute') takes it on the f64 difference-form
+ * distances d of the f32 points (_linkage.pyx: mst_from_mutual_reachability).  X, ldx, N, D as for dic_optics_order (D <= 256, D % 4 == 0, N < 2^30, X and
+ * the workspace 16-B aligned).  core (N) f64, DEVICE, in: the distances to the min_samples-th neighbour, the point itself counted, UNROUNDED --
+ * dic_knn_kth_distance(k = min_samples) supplies the values, and its distances are bit for bit this file's (csrc/dic_exactd2.h): every edge into a sparse
+ * point weighs exactly that point's core distance, and the tie-breaking by index relies on equal bits.
+ *   dic_hdbscan_mst: ordering (N) int32, reachability (N) f64, predecessor (N) int32, all OVERWRITTEN.  reachability = inf, predecessor = -1, point 0 is first;
+ *       N - 1 times: the current point p is in the tree; every q outside it with mr(p, q) < reachability[q] (strictly) takes that value and predecessor p; the
+ *       point outside the tree of smallest reachability (ties: the smallest index) is appended to ordering and becomes p.  reachability[q] is the weight at
+ *       which q joined (inf for point 0) and predecessor[q] its neighbour in the tree (-1 for point 0); sklearn's edge record of step i is
+ *       (ordering[i], ordering[i + 1], reachability[ordering[i + 1]]).  One launch per step, as dic_optics_order: the N - 1 launches are enqueued on `stream`
+ *       without synchronising (N = 1: none), the results are complete when the stream has drained, and no launch waits for another workgroup.  The
+ *       workspace (dic_hdbscan_workspace(N, D) bytes, O(N)) holds the in-tree flags, the workgroup minima, the current point and the arrival counter.
+ *       Deterministic results. */
+size_t dic_hdbscan_workspace(int64_t N, int D);
+int dic_hdbscan_mst(const float* X, long ldx, int64_t N, int D, const double* core, int32_t* ordering, double* reachability, int32_t* predecessor,
+                    void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 /* Consensus clustering from a label matrix and the average-linkage agglomeration of its consensus distance (csrc/dic_consensus.hip): the p2 / p4
  * `--cluster_method consensus` branches (p4_clustering_final.py:241-287 reads labels "generated outside": Monti-style consensus clustering with a k-means
  * base clusterer, ConsensusClusterPlus' conventions).  L (N, ldl) uint8, DEVICE, 16-B aligned: L[i, h] for h < H is the label 0..K-1 (K <= 254) of point i in
