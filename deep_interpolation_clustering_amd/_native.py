@@ -144,6 +144,8 @@ SIGNATURES = {
     'dic_consensus_pairs': (_i, [_p, C.c_long, C.c_int64, _i, _p, _i, _p, _p, _p, _p, _sz, _p]),
     'dic_linkage_average_workspace': (_sz, [C.c_int64]),
     'dic_linkage_average': (_i, [_p, C.c_int64, _p, _p, _sz, _p]),
+    'dic_ward_workspace': (_sz, [C.c_int64, _i]),
+    'dic_ward_linkage': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, _sz, _p]),
 }
 
 

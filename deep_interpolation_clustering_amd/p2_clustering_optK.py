@@ -33,6 +33,12 @@ tree does not depend on it).  The walk goes to <metric>_hdbscan_aligned/plot/hdb
 its neighbour in the tree, the weight it joined at), the per-size table to plot/hdbscan_sizes.csv (min_cluster_size, n_clusters, n_noise, silhouette,
 denoise_silhouette) and the labels to plot/hdbscan_labels.csv, one column mcs<size> per size.
 
+``--cluster_method ward`` (no upstream counterpart): Ward's agglomerative clustering of the training latents on the GPU (ward.py: no N x N matrix, one launch
+per step of the nearest-neighbour chain over the live centroids).  ONE tree serves every K: it is cut at K = 2..k_max, and per K the merge height, the mean
+distance to the nearest centre on the training and the validation latents (the elbow's distortion) and the --internal_metrics go to
+<metric>_ward_aligned/plot/ward_k.csv; the dendrogram goes to plot/ward_linkage.csv (scipy's Z, %.17g) and the 0-based labels to plot/ward_labels.csv, one
+column k<K> per K.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -55,13 +61,14 @@ from .kmeans import KMeans, seed_draw_count
 from .knn import k_distance_graph
 from .optics import OPTICS
 from .utils import logger, print_dict_byline
+from .ward import Ward as WardLinkage
 
 np.random.seed(123)        # p2_clustering_optK.py:23
 
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward'])
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -485,6 +492,62 @@ class Hdbscan(object):
         return df
 
 
+class Ward(object):
+    """One Ward tree of the training latents (``ward.Ward``), cut at K = 2..``k_max``.  Per K: the labels, the height of the merge that takes K clusters to
+    K - 1, the mean distance to the nearest centre on the training and the validation latents (the elbow's distortion) and the ``internal_metrics`` as
+    ``KM`` computes them -- one shared pair pass per K, ``metric_sample`` honoured -- logged per K as ``KM`` logs.  Writes plot/ward_linkage.csv (Z: left,
+    right, height, size, %.17g), plot/ward_k.csv (k, height, train_distortion, valid_distortion, the metrics) and plot/ward_labels.csv (columns k2..k<k_max>,
+    0-based) and returns the per-K table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.  ``fit_`` keeps the
+    fitted ``ward.Ward`` of the last run that computed one."""
+    FILES = ('ward_linkage.csv', 'ward_k.csv', 'ward_labels.csv')
+
+    def __init__(self, k_max, out_path, internal_metrics, metric_sample=0):
+        self.ks = list(range(2, k_max + 1))
+        self.metric_sample = metric_sample
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.internal_metrics_names = list(internal_metrics)
+        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
+        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self.fit_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fit_ = None
+        linkage_csv, k_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (linkage_csv, k_csv, labels_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(linkage_csv))
+            return pd.read_csv(k_csv, float_precision='round_trip')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        Vd = torch.as_tensor(valid_data['hidden'], dtype=torch.float32, device=dev)
+        fit = WardLinkage(ks=self.ks).fit(Xd)
+        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
+        rows = []
+        for k in self.ks:
+            logger.info('Running K: {}'.format(k))
+            labels = fit.labels_by_k_[k]
+            centers = fit.cluster_centers_by_k_[k]
+            train_d = float(fit.nearest_distance(Xd, centers).mean())
+            valid_d = float(fit.nearest_distance(Vd, centers).mean())
+            if self.metric_sample and self.metric_sample < len(labels):
+                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
+                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
+            else:
+                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
+                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
+            logger.info('k: {}, height: {:.4f}, train: {:.4f}, valid: {:.4f} '.format(k, fit.heights_by_k_[k], train_d, valid_d)
+                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+            rows.append([k, fit.heights_by_k_[k], train_d, valid_d] + vals)
+        df = pd.DataFrame(rows, columns=['k', 'height', 'train_distortion', 'valid_distortion'] + self.internal_metrics_names)
+        pd.DataFrame(fit.linkage_, columns=['left', 'right', 'height', 'size']).to_csv(linkage_csv, index=False, float_format='%.17g')
+        df.to_csv(k_csv, index=False, float_format='%.17g')
+        pd.DataFrame({'k{}'.format(k): fit.labels_by_k_[k] for k in self.ks}).to_csv(labels_csv, index=False)
+        logger.info('Saved for {}!.'.format(linkage_csv))
+        self.fit_ = fit
+        return df
+
+
 class Consensus(object):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
@@ -575,8 +638,13 @@ class Cluster(object):
                     hd = Hdbscan(min_samples=self.feat_dim + 1, min_cluster_sizes=sizes, out_path=self.out_path)
                     results[metric] = hd.train(self.train_data, self.valid_data)
                 continue
+            if self.args.cluster_method == 'ward':
+                if dist.rank() == 0:            # one tree, on rank 0; the other ranks wait at main's barrier
+                    wd = Ward(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.metric_sample)
+                    results[metric] = wd.train(self.train_data, self.valid_data)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus and hdbscan are on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan and ward are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

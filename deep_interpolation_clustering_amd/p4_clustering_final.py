@@ -15,6 +15,9 @@ training centre, exactly as the dbscan branch does it; writes <cohort>_mcs-<min_
 re-numbers the training clusters by sbp (generate_align_map) and applies that map to the training and the validation cohort (upstream leaves the test cohort
 out); writes <cohort>_<k>.npy.  Upstream's csv files were "generated outside"; a missing one is first computed here by consensus clustering of that cohort's
 latents on the GPU (consensus.py) and written.
+``ward`` (no upstream counterpart; the kmeans branch with a tree in place of the fits): the Ward tree of the training latents on the GPU (ward.py) cut at
+--num_clusters, the clusters re-numbered by sbp, the centres re-ordered with the map; the training cohort keeps its tree labels, validation and test get the
+nearest training centre; writes <cohort>_<k>.npy.
 """
 import argparse
 import copy
@@ -30,13 +33,14 @@ from .hdbscan import HDBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
 from .utils import logger, print_dict_byline
+from .ward import Ward
 
 np.random.seed(123)        # p4_clustering_final.py:24
 
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
@@ -166,6 +170,29 @@ class Cluster(object):
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
             np.save(f, data)
 
+    def _ward(self, cohorts, overwrite):
+        """The kmeans branch with one Ward tree of the training latents in place of the k-means fits: the tree is cut at --num_clusters, generate_align_map
+        orders the clusters by sbp and the centres (the means of the members) are re-ordered with the map.  The training cohort keeps its tree labels,
+        aligned; validation and test get ``predict``, the nearest aligned training centre.  A training point's tree label need not be its nearest centre
+        -- Ward merges greedily and never reassigns a point -- so the training ids are NOT ``predict`` of the training latents, unlike the kmeans branch."""
+        k = self.args.num_clusters
+        logger.info('==> Generate the Ward results with opt-k: {}'.format(k))
+        model = Ward(n_clusters=k).fit(self.train_data['hidden'])
+        raw = np.array(model.labels_)
+        align_map, aligned, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
+        independent = copy.deepcopy(model.cluster_centers_)
+        for old, new in align_map.items():
+            model.cluster_centers_[new] = independent[old]
+        for cohort, data in cohorts:
+            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, k))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            data['cluster_id'] = aligned if cohort == 'training' else model.predict(data['hidden'])
+            del data['ob'], data['padding_mask']
+            np.save(f, data)
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+
     def _raw_consensus(self, cohort, data):
         """The raw consensus labels of a cohort for k = num_clusters, 0-based as generate_align_map wants them (p4:247-253): column k<num_clusters> of
         raw_consensus_result/<cohort>_consensus.csv, computed and written first where the file is missing."""
@@ -254,8 +281,10 @@ class Cluster(object):
                 self._consensus(overwrite)
             elif self.args.cluster_method == 'hdbscan':
                 self._hdbscan(cohorts, overwrite)
+            elif self.args.cluster_method == 'ward':
+                self._ward(cohorts, overwrite)
             else:
-                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus' and 'hdbscan' are on the accelerated path: upstream's 'optics' branch of p4 is an "
+                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus', 'hdbscan' and 'ward' are on the accelerated path: upstream's 'optics' branch of p4 is an "
                                           "empty `pass` (p2 has the OPTICS fit)")
 
 

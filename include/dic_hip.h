@@ -692,6 +692,21 @@ int dic_consensus_pairs(const unsigned char* L, long ldl, int64_t N, int H, cons
 size_t dic_linkage_average_workspace(int64_t N);
 int dic_linkage_average(double* D, int64_t N, double* records, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* Ward's agglomerative clustering without the distance matrix (csrc/dic_ward.hip): scipy.cluster.hierarchy.linkage(X, 'ward') on the f32 points X (N, ldx),
+ * DEVICE, 16-B aligned, D % 4 == 0 <= 256, ldx % 4 == 0, 2 <= N < 2^30; X is only read.  A live cluster i has a size n_i, the f64 coordinate sums S_i and the
+ * centroid C_i = S_i / n_i (one rounded division per coordinate when the cluster is made); d2(i, j) = (2 n_i n_j / (n_i + n_j)) * sum_k (C_i[k] - C_j[k])^2, the
+ * sum in f64 in dic_exactd2.h's order, the factor in f64 and symmetric in i and j, nothing contracted; the height of a merge is sqrt(d2).  A merge of a < b
+ * leaves S_b = S_a + S_b, n_b = n_a + n_b, C_b = S_b / n_b, n_a = 0.
+ *   dic_ward_linkage: the nearest-neighbour chain with scipy's tie-breaking, as dic_linkage_average states it (an empty chain starts at the smallest live
+ *       index; the neighbour is the lexicographic minimum of (d2, index); chain[-2] wins a tie).  records (N - 1, 4) f64 OVERWRITTEN: (a, b, height,
+ *       n_a + n_b) per merge in the order the merges happen: NOT sorted by height and not relabelled (ward.ward_linkage does both on the host).  One launch per
+ *       repeat of the chain's inner loop -- a row pass over the live centroids by at most 256 workgroups, whose minimum the last workgroup to arrive takes in
+ *       the same launch, as dic_optics_order -- 3 (N - 1) launches in all, enqueued on `stream` without synchronising; no workgroup waits for another.  The
+ *       workspace (dic_ward_workspace(N, D) bytes, linear in N: S and C, 2 x 8 N D bytes, the sizes, the chain, the workgroup minima and the state) ends
+ *       with 256 B that begin with four int32: chain length, merges done, launches that pushed or merged, smallest live index.  Deterministic. */
+size_t dic_ward_workspace(int64_t N, int D);
+int dic_ward_linkage(const float* X, long ldx, int64_t N, int D, double* records, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
