@@ -146,6 +146,10 @@ SIGNATURES = {
     'dic_linkage_average': (_i, [_p, C.c_int64, _p, _p, _sz, _p]),
     'dic_ward_workspace': (_sz, [C.c_int64, _i]),
     'dic_ward_linkage': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, _sz, _p]),
+    'dic_gmm_workspace': (_sz, [C.c_int64, _i, _i, _i]),
+    'dic_gmm_em_iter': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _i, _p, _sz, _p]),
+    'dic_gmm_estep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_gmm_mstep_labels': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
 }
 
 

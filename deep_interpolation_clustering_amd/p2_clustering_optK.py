@@ -39,6 +39,12 @@ distance to the nearest centre on the training and the validation latents (the e
 <metric>_ward_aligned/plot/ward_k.csv; the dendrogram goes to plot/ward_linkage.csv (scipy's Z, %.17g) and the 0-based labels to plot/ward_labels.csv, one
 column k<K> per K.
 
+``--cluster_method gmm`` (no upstream counterpart): Gaussian mixtures with --gmm_covariance_type diag | spherical covariances, fitted to the training latents on
+the GPU for K = 2..k_max with --n_init restarts each (gmm.py: f64 EM, one pass over the latents per iteration, the restarts advancing together).  Per K the
+lower bound, BIC and AIC of the fit itself -- a likelihood-based criterion for K that needs no reference sets -- the iterations, the mean log-likelihood of the
+validation cohort and the --internal_metrics of the hard labels go to <metric>_gmm_aligned/plot/gmm_k.csv, the 0-based labels to plot/gmm_labels.csv, one
+column k<K> per K.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -54,6 +60,7 @@ import torch
 from . import cluster_stats, dist
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
+from .gmm import gmm_sweep
 from .hdbscan import hdbscan_sizes
 from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
@@ -68,7 +75,7 @@ np.random.seed(123)        # p2_clustering_optK.py:23
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm'])
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -81,6 +88,7 @@ def get_arguments(argv=None):
     p.add_argument('--consensus_p_item', type=float, default=0.8, help='(extra) fraction of the points in a resample')
     p.add_argument('--hdbscan_min_cluster_size', type=int, nargs='+', default=None,
                    help='(extra) min_cluster_size values of --cluster_method hdbscan; default feat_dim + 1')
+    p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical'], help='(extra) covariances of --cluster_method gmm')
     p.add_argument('--metric_sample', type=int, default=0, help='(extra) subsample size for the O(N^2) validity indices; 0 = all')
     return p.parse_args(argv)
 
@@ -548,6 +556,64 @@ class Ward(object):
         return df
 
 
+class Gmm(object):
+    """Gaussian mixtures of the training latents (``gmm.gmm_sweep``) for K = 2..``k_max``, ``n_init`` restarts each.  Per K: the lower bound, BIC and AIC on the
+    training latents, the iterations and whether the winning restart converged, the mean log-likelihood of the validation cohort under the training model, and
+    the ``internal_metrics`` of the hard labels as ``KM`` computes them -- one shared pair pass per K, ``metric_sample`` honoured -- logged per K as ``KM``
+    logs.  Writes plot/gmm_k.csv (k, lower_bound, bic, aic, n_iter, converged, valid_score, the metrics) and plot/gmm_labels.csv (columns k2..k<k_max>,
+    0-based) and returns the per-K table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.  ``fits_`` keeps the
+    fitted models {K: ``gmm.GaussianMixture``} of the last run that computed them."""
+    FILES = ('gmm_k.csv', 'gmm_labels.csv')
+
+    def __init__(self, k_max, out_path, internal_metrics, n_init=1, covariance_type='diag', metric_sample=0):
+        self.ks = list(range(2, k_max + 1))
+        self.n_init, self.covariance_type = n_init, covariance_type
+        self.metric_sample = metric_sample
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.internal_metrics_names = list(internal_metrics)
+        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
+        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self.fits_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fits_ = None
+        k_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (k_csv, labels_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(k_csv))
+            return pd.read_csv(k_csv, float_precision='round_trip')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        Vd = torch.as_tensor(valid_data['hidden'], dtype=torch.float32, device=dev)
+        fits = gmm_sweep(Xd, self.ks, covariance_type=self.covariance_type, n_init=self.n_init)
+        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
+        rows = []
+        for k in self.ks:
+            logger.info('Running K: {}'.format(k))
+            fit = fits[k]
+            labels = np.unique(fit.labels_, return_inverse=True)[1].astype(np.int64)          # (a component without a row of its own is skipped by the indices)
+            bic, aic, valid = float(fit.bic(Xd)), float(fit.aic(Xd)), float(fit.score(Vd))
+            if labels.max() < 1:          # (the indices need two clusters)
+                vals = [float('nan')] * len(self.internal_metrics)
+            elif self.metric_sample and self.metric_sample < len(labels):
+                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
+                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
+            else:
+                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
+                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
+            logger.info('k: {}, lower_bound: {:.4f}, bic: {:.1f}, aic: {:.1f}, n_iter: {}, valid: {:.4f} '.format(k, fit.lower_bound_, bic, aic, fit.n_iter_,
+                                                                                                                valid)
+                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+            rows.append([k, fit.lower_bound_, bic, aic, fit.n_iter_, int(fit.converged_), valid] + vals)
+        df = pd.DataFrame(rows, columns=['k', 'lower_bound', 'bic', 'aic', 'n_iter', 'converged', 'valid_score'] + self.internal_metrics_names)
+        df.to_csv(k_csv, index=False, float_format='%.17g')
+        pd.DataFrame({'k{}'.format(k): fits[k].labels_ for k in self.ks}).to_csv(labels_csv, index=False)
+        logger.info('Saved for {}!.'.format(k_csv))
+        self.fits_ = fits
+        return df
+
+
 class Consensus(object):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
@@ -642,6 +708,12 @@ class Cluster(object):
                 if dist.rank() == 0:            # one tree, on rank 0; the other ranks wait at main's barrier
                     wd = Ward(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.metric_sample)
                     results[metric] = wd.train(self.train_data, self.valid_data)
+                continue
+            if self.args.cluster_method == 'gmm':
+                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
+                    gm = Gmm(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gmm_covariance_type,
+                             self.args.metric_sample)
+                    results[metric] = gm.train(self.train_data, self.valid_data)
                 continue
             if self.args.cluster_method != 'kmeans':
                 raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan and ward are on the accelerated path")

@@ -18,6 +18,9 @@ latents on the GPU (consensus.py) and written.
 ``ward`` (no upstream counterpart; the kmeans branch with a tree in place of the fits): the Ward tree of the training latents on the GPU (ward.py) cut at
 --num_clusters, the clusters re-numbered by sbp, the centres re-ordered with the map; the training cohort keeps its tree labels, validation and test get the
 nearest training centre; writes <cohort>_<k>.npy.
+``gmm`` (no upstream counterpart; the kmeans branch with a mixture in place of the centres): a Gaussian mixture of --num_clusters diagonal components fitted
+to the training latents on the GPU (gmm.py), the components re-numbered by sbp -- weights, means and covariances permuted with the map -- and every cohort
+labelled by ``predict`` of that one model; writes <cohort>_<k>.npy with ``cluster_id`` and ``cluster_prob``, the (N, K) f32 responsibilities.
 """
 import argparse
 import copy
@@ -29,6 +32,7 @@ import pandas as pd
 
 from . import cluster_stats
 from .dbscan import DBSCAN
+from .gmm import GaussianMixture
 from .hdbscan import HDBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
@@ -40,7 +44,7 @@ np.random.seed(123)        # p4_clustering_final.py:24
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
@@ -193,6 +197,33 @@ class Cluster(object):
             np.save(f, data)
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
 
+    def _gmm(self, cohorts, overwrite):
+        """The kmeans branch with a Gaussian mixture in place of the centres: fitted on the training cohort, generate_align_map orders the components by sbp
+        and the model's weights, means and covariances are permuted with the map, as the kmeans branch permutes its centres.  Every cohort, training
+        included, is labelled by ``predict`` of that model; ``cluster_prob`` holds its responsibilities, so ``cluster_id`` is their argmax."""
+        k = self.args.num_clusters
+        logger.info('==> Generate the Gaussian mixture results with opt-k: {}'.format(k))
+        model = GaussianMixture(n_components=k, n_init=10).fit(self.train_data['hidden'])
+        raw = model.predict(self.train_data['hidden']).astype(np.int64)
+        if len(set(raw)) != k:
+            raise ValueError('the Gaussian mixture left {} of its {} components without a training encounter: choose a smaller --num_clusters'.format(
+                k - len(set(raw)), k))
+        align_map, _, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
+        order = np.empty(k, dtype=np.int64)
+        for old, new in align_map.items():
+            order[new] = old
+        model.reorder(order)
+        for cohort, data in cohorts:
+            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, k))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            data['cluster_id'] = model.predict(data['hidden'])
+            data['cluster_prob'] = model.predict_proba(data['hidden']).astype(np.float32)
+            del data['ob'], data['padding_mask']
+            np.save(f, data)
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+
     def _raw_consensus(self, cohort, data):
         """The raw consensus labels of a cohort for k = num_clusters, 0-based as generate_align_map wants them (p4:247-253): column k<num_clusters> of
         raw_consensus_result/<cohort>_consensus.csv, computed and written first where the file is missing."""
@@ -283,6 +314,8 @@ class Cluster(object):
                 self._hdbscan(cohorts, overwrite)
             elif self.args.cluster_method == 'ward':
                 self._ward(cohorts, overwrite)
+            elif self.args.cluster_method == 'gmm':
+                self._gmm(cohorts, overwrite)
             else:
                 raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus', 'hdbscan' and 'ward' are on the accelerated path: upstream's 'optics' branch of p4 is an "
                                           "empty `pass` (p2 has the OPTICS fit)")

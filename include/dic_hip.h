@@ -707,6 +707,38 @@ int dic_linkage_average(double* D, int64_t N, double* records, void* workspace, 
 size_t dic_ward_workspace(int64_t N, int D);
 int dic_ward_linkage(const float* X, long ldx, int64_t N, int D, double* records, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* Gaussian mixtures with diagonal (cov_type 0) or spherical (cov_type 1) covariances by EM, every operation in f64 (csrc/dic_gmm.hip; sklearn.mixture.
+ * GaussianMixture's model).  X (N, ldx) f32, DEVICE, 16-B aligned, only read; D % 4 == 0 <= 256, ldx % 4 == 0, 2 <= N < 2^30, 1 <= K <= DIC_MAX_CLUSTERS,
+ * n_runs >= 1; D0 (1 <= D0 <= D) is the true feature count, the columns D0 .. D - 1 are zero padding and add nothing, their variances are skipped.  All
+ * parameters are f64 on the DEVICE, per restart: weights (n_runs, K), means (n_runs, K, D), variances (n_runs, K, D) (spherical: one value repeated over D);
+ * shift (D) is shared.  Every x enters as x' = (double)x - shift, and `means` holds mu' = mu - shift.
+ *   E-step: M_ik = sum_d (x'_id - mu'_kd)^2 / v_kd;  log p_ik = log w_k - (D0 log 2 pi + M_ik) / 2 - (sum_{d < D0} log v_kd) / 2;  lse_i = logsumexp_k log p_ik
+ *       with the maximum subtracted;  log r_ik = log p_ik - lse_i;  the lower bound is mean_i lse_i.
+ *   M-step: n_k = sum_i r_ik + 10 * 2^-52;  mu'_k = sum_i r_ik x'_i / n_k;  v_kd = sum_i r_ik x'_id^2 / n_k - mu'_kd^2 + reg_covar (spherical: the mean over
+ *       d < D0);  w_k = (n_k / N) / sum_k (n_k / N).
+ * Sums over rows are per-workgroup f64 partials in the workspace (dic_gmm_workspace bytes, 16-B aligned), added in block order by a second kernel: no
+ * floating-point atomics, two calls give the same bits, and a restart's bits do not depend on the restarts beside it.  Nothing synchronises `stream`.
+ *   dic_gmm_em_iter: one E+M pass for every restart whose done flag is clear; done restarts keep their parameters.  status (n_runs, DIC_GMM_STATUS_WORDS) f64
+ *       IN/OUT: [0] done, [1] iterations run, [2] 1 if stopped by the tolerance, [3] the last lower bound (set -inf before the first iteration), [4] tol (IN),
+ *       [5] max_iter (IN), [6] internal, [7] unused; zero [0..2] before the first iteration.  The pass appends its lower bound to
+ *       lower_bounds[run * lb_stride + iterations] (dropped beyond lb_stride), and sets done when |lb_t - lb_(t-1)| < tol or iterations reaches max_iter; the
+ *       M-step of the converging iteration is kept, as in sklearn.
+ *   dic_gmm_estep: the E-step of ONE parameter set.  Outputs, each optional (NULL): lse (N) f64, log_resp (N, K) f64, labels (N) int32 (the first maximum of
+ *       log p), sum_lse (1) f64 (sum_i lse_i in fixed order).
+ *   dic_gmm_mstep_labels: the M-step from hard labels (labels (n_runs, N) int32: one-hot responsibilities; a label outside 0 .. K - 1 gives a row of zeros) or
+ *       from responsibilities (resp (n_runs, N, K) f64) -- exactly one of the two -- through the accumulation of the EM pass. */
+#define DIC_GMM_STATUS_WORDS 8
+size_t dic_gmm_workspace(int64_t N, int D, int K, int n_runs);
+int dic_gmm_em_iter(const float* X, long ldx, int64_t N, int D, int D0, int K, int n_runs, int cov_type, double reg_covar, const double* shift, double* weights,
+                    double* means, double* variances, double* status, double* lower_bounds, int lb_stride, void* workspace, size_t workspace_bytes,
+                    dic_stream_t stream);
+int dic_gmm_estep(const float* X, long ldx, int64_t N, int D, int D0, int K, const double* shift, const double* weights, const double* means,
+                  const double* variances, double* lse, double* log_resp, int32_t* labels, double* sum_lse, void* workspace, size_t workspace_bytes,
+                  dic_stream_t stream);
+int dic_gmm_mstep_labels(const float* X, long ldx, int64_t N, int D, int D0, int K, int n_runs, int cov_type, double reg_covar, const double* shift,
+                         const int32_t* labels, const double* resp, double* weights, double* means, double* variances, void* workspace,
+                         size_t workspace_bytes, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
