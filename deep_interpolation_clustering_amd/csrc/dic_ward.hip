@@ -14,36 +14,24 @@
 // Every expression whose rounding must not depend on contraction (the factor, the product with the sum, the differences, the sums S and the division) is
 // under `#pragma clang fp contract(off)`; the fma chain is written as fma.  DESIGN.md's consensus section has the reason.
 //
-// A STEP (wd_step_kernel) IS ONE LAUNCH, the grid form of dic_optics.hip's op_step_kernel: at most 256 workgroups of 16 waves, and never two of them on one
-// CU (each reserves 96 KiB of the CU's 160 KiB of LDS, WD_LDS_HOLD, which it does not touch).  Every wave reads the chain's state where the previous launch
-// left it and holds C_x in registers (32 B per lane: two 16-B loads); it then takes rows q = wave, wave + #waves, .., four at a time: a dead row (and x
-// itself) costs one size load and no row load, a live one its 32 B per lane, the distance, and enters the wave's running minimum of (d2, index).  The wave
-// that meets chain[-2] keeps its distance, d_prev.  Wave minima and d_prev meet in LDS, and the workgroup's partial (d2, index, d_prev; -1 = not met) goes
-// to its 32-B slot of `part`.
-// THE GRID'S MINIMUM is taken by the workgroup that arrives last, in the same launch, exactly as in dic_optics.hip: one lane stores the partial with 8-B
-// write-through (sc1) stores, waits for them (vmcnt(0)) and adds 1 to the ticket, an agent-scope atomic; the workgroup whose add returns gridDim.x - 1 knows
-// every partial is in memory, reads them with sc1 loads (past its L1, which other CUs' stores never refresh) behind a workgroup barrier its adding wave
-// joined, and reduces them.  It then does what lk_step_kernel's tail does: it compares with d_prev and either pushes y or merges -- S_b, C_b, the sizes, the
-// record, the chain length, the merge and step counts -- and sets the ticket to 0.  No workgroup waits for another: every launch ends on its own.  Nothing
-// the last workgroup writes is read in its own launch (every other workgroup has read the state and left its row loop before it took its ticket; the last
-// workgroup itself reads S_a, S_b and the sizes it is about to overwrite first, behind a barrier where another thread writes them), and everything a launch
-// reads besides `part` was written by an earlier launch.
+// A STEP (wd_step_kernel) IS ONE LAUNCH in dic_gridstep.h's hand-off form (its constants, gs_before, gs_post, the past-L1 loads, the host loop; the proof
+// is there).  Every wave reads the chain's state where the previous launch left it and holds C_x in registers (32 B per lane: two 16-B loads); it then
+// takes rows q = wave, wave + #waves, .., four at a time: a dead row (and x itself) costs one size load and no row load, a live one its 32 B per lane, the
+// distance, and enters the wave's running minimum of (d2, index).  The wave that meets chain[-2] keeps its distance, d_prev.  Wave minima and d_prev meet in
+// LDS, and the workgroup's partial (d2, index, d_prev; -1 = not met) goes to its 32-B slot of `part`.
+// The workgroup that arrives last reduces the partials and does what lk_step_kernel's tail does: it compares with d_prev and either pushes y or merges --
+// S_b, C_b, the sizes, the record, the chain length, the merge and step counts -- and sets the ticket to 0.  What the hand-off asks of it: of the state it
+// overwrites it reads S_a, S_b (each coordinate by the thread that writes it), the sizes and the cursor first, behind a barrier where another thread writes
+// them.
 // THE SMALLEST LIVE INDEX only grows (a merge kills the smaller name), so a cursor serves the fresh chain: when a merge kills the cursor's cluster a, the
 // last workgroup moves it to the first live index above a -- b at the latest; the sizes it scans, those strictly between a and b, nobody writes in this
 // launch.  The scans of all merges together pass over every index once.
 // The host enqueues one init kernel and 3 (N - 1) steps -- a launch pushes or merges, and a fresh chain pushes two -- and returns; a step that finds
 // N - 1 merges done returns at once.  The host never reads an intermediate result.  Two calls give the same bits.
-#include "dic_common.h"
+#include "dic_gridstep.h"
 
 namespace dic {
 
-constexpr int WD_WAVES = 16;                    // waves per workgroup
-constexpr int WD_THREADS = WD_WAVES * kWave;
-constexpr int WD_MAX_BLOCKS = kNumCU;           // one workgroup per CU at most: the hand-off of the partials is the one-per-CU form
-constexpr int WD_LDS_HOLD = 96 * 1024;          // dynamic LDS a step asks for and never touches: more than half a CU's 160 KiB, so that no second workgroup of
-                                                // a step can be placed on the same CU
-constexpr int WD_UNROLL = 4;                    // rows in flight per wave
-constexpr int WD_NONE = 0x7fffffff;             // the index of "no live row besides x"
 constexpr int WD_PART = 4;                      // 8-B words of a workgroup's partial: d2, index, d_prev, (unused)
 
 typedef double wd_f64x2 __attribute__((ext_vector_type(2)));
@@ -61,20 +49,16 @@ static WdLayout wd_layout(int64_t N, int D) {
     o.size = o.C + align_up((size_t)N * row, 256);
     o.chain = o.size + align_up((size_t)N * sizeof(int), 256);
     o.part = o.chain + align_up((size_t)N * sizeof(int), 256);
-    o.state = o.part + align_up((size_t)WD_MAX_BLOCKS * WD_PART * sizeof(unsigned long long), 256);
+    o.state = o.part + align_up((size_t)GS_MAX_BLOCKS * WD_PART * sizeof(unsigned long long), 256);
     o.total = o.state + 256;
     return o;
 }
-
-static int wd_blocks(int64_t N) { return (int)max((int64_t)1, min((int64_t)WD_MAX_BLOCKS, (N + WD_WAVES - 1) / WD_WAVES)); }
 
 struct WdArgs {
     int n, d;
     double* S; double* C; int* size; int* chain;
     unsigned long long* part; WdState* st; double* rec;
 };
-
-__device__ __forceinline__ bool wd_before(double va, int ia, double vb, int ib) { return va < vb || (va == vb && ia < ib); }
 
 // this lane's four coordinates of row `row` of an (n, d) f64 matrix (zeros beyond d); d % 4 == 0, rows 32-B aligned
 __device__ __forceinline__ WdRow wd_load(const double* M, int d, size_t row) {
@@ -147,26 +131,26 @@ __global__ __launch_bounds__(256) void wd_init_kernel(const float* X, long ldx, 
     }
 }
 
-// The last workgroup of a step: every partial is in memory.  The grid's (d2, index) and d_prev, in every thread.  nblk <= WD_MAX_BLOCKS = 256 partials, one
+// The last workgroup of a step: every partial is in memory.  The grid's (d2, index) and d_prev, in every thread.  nblk <= GS_MAX_BLOCKS = 256 partials, one
 // per thread of the first four waves, read past L1.
 __device__ __forceinline__ void wd_pick(const WdArgs& a, int nblk, double& br, int& bi, double& dp, double* s_r, int* s_i, double* s_d) {
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
     br = __builtin_inf();
-    bi = WD_NONE;
+    bi = GS_NONE;
     dp = -1.0;
     if (tid < nblk) {
         const unsigned long long* p = a.part + (size_t)WD_PART * tid;
-        br = __longlong_as_double((long long)__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        bi = (int)(unsigned)__hip_atomic_load(p + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        dp = __longlong_as_double((long long)__hip_atomic_load(p + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        br = gs_load_f64(p);
+        bi = gs_load_int(p + 1);
+        dp = gs_load_f64(p + 2);
     }
-    if (w < WD_MAX_BLOCKS / kWave) {
+    if (w < GS_MAX_BLOCKS / kWave) {
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) {
             const double orr = __shfl_xor(br, m);
             const int oi = __shfl_xor(bi, m);
             const double od = __shfl_xor(dp, m);
-            if (wd_before(orr, oi, br, bi)) { br = orr; bi = oi; }
+            if (gs_before(orr, oi, br, bi)) { br = orr; bi = oi; }
             dp = fmax(dp, od);          // (one workgroup met chain[-2]; the others hold -1)
         }
     }
@@ -175,8 +159,8 @@ __device__ __forceinline__ void wd_pick(const WdArgs& a, int nblk, double& br, i
     __syncthreads();
     br = s_r[0]; bi = s_i[0]; dp = s_d[0];
 #pragma unroll
-    for (int k = 1; k < WD_MAX_BLOCKS / kWave; ++k) {
-        if (wd_before(s_r[k], s_i[k], br, bi)) { br = s_r[k]; bi = s_i[k]; }
+    for (int k = 1; k < GS_MAX_BLOCKS / kWave; ++k) {
+        if (gs_before(s_r[k], s_i[k], br, bi)) { br = s_r[k]; bi = s_i[k]; }
         dp = fmax(dp, s_d[k]);
     }
 }
@@ -184,25 +168,25 @@ __device__ __forceinline__ void wd_pick(const WdArgs& a, int nblk, double& br, i
 // The first live index strictly between a and b, or b: by the whole workgroup, the result in every thread.  Nobody writes these sizes in this launch.
 __device__ __forceinline__ int wd_next_live(const int* size, int a, int b, int* s_i) {
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
-    for (int base = a + 1; base < b; base += WD_THREADS) {
+    for (int base = a + 1; base < b; base += GS_THREADS) {
         const int i = base + tid;
         const bool live = i < b && size[i] > 0;
         const unsigned long long m = __ballot(live);
         __syncthreads();          // (an earlier round, or wd_pick, has been read)
-        if (lane == 0) s_i[w] = m ? base + w * kWave + (int)__builtin_ctzll(m) : WD_NONE;
+        if (lane == 0) s_i[w] = m ? base + w * kWave + (int)__builtin_ctzll(m) : GS_NONE;
         __syncthreads();
-        int found = WD_NONE;
+        int found = GS_NONE;
 #pragma unroll
-        for (int k = 0; k < WD_WAVES; ++k) found = min(found, s_i[k]);
-        if (found != WD_NONE) return found;
+        for (int k = 0; k < GS_WAVES; ++k) found = min(found, s_i[k]);
+        if (found != GS_NONE) return found;
     }
     return b;
 }
 
-__global__ __launch_bounds__(WD_THREADS) void wd_step_kernel(WdArgs a) {
-    __shared__ double s_r[WD_WAVES];
-    __shared__ double s_d[WD_WAVES];
-    __shared__ int s_i[WD_WAVES];
+__global__ __launch_bounds__(GS_THREADS) void wd_step_kernel(WdArgs a) {
+    __shared__ double s_r[GS_WAVES];
+    __shared__ double s_d[GS_WAVES];
+    __shared__ int s_i[GS_WAVES];
     __shared__ int s_last;
     const int tid = threadIdx.x, lane = tid & (kWave - 1), w = tid >> 6;
     const int n = a.n, d = a.d;
@@ -223,29 +207,29 @@ __global__ __launch_bounds__(WD_THREADS) void wd_step_kernel(WdArgs a) {
     const int nx = a.size[x];
     const WdRow cx = wd_load(a.C, d, (size_t)x);
     double br = __builtin_inf(), dp = -1.0;
-    int bi = WD_NONE;
-    const int stride = gridDim.x * WD_WAVES;
-    for (int q0 = blockIdx.x * WD_WAVES + w; q0 < n; q0 += WD_UNROLL * stride) {
-        int nq[WD_UNROLL];
-        WdRow cq[WD_UNROLL];
+    int bi = GS_NONE;
+    const int stride = gridDim.x * GS_WAVES;
+    for (int q0 = blockIdx.x * GS_WAVES + w; q0 < n; q0 += GS_UNROLL * stride) {
+        int nq[GS_UNROLL];
+        WdRow cq[GS_UNROLL];
 #pragma unroll
-        for (int u = 0; u < WD_UNROLL; ++u) {
+        for (int u = 0; u < GS_UNROLL; ++u) {
             const int q = q0 + u * stride;
             nq[u] = (q < n && q != x) ? a.size[q] : 0;
         }
 #pragma unroll
-        for (int u = 0; u < WD_UNROLL; ++u) {
+        for (int u = 0; u < GS_UNROLL; ++u) {
             const int q = q0 + u * stride;
             cq[u] = cx;
             if (nq[u] > 0) cq[u] = wd_load(a.C, d, (size_t)q);
         }
 #pragma unroll
-        for (int u = 0; u < WD_UNROLL; ++u) {
+        for (int u = 0; u < GS_UNROLL; ++u) {
             const int q = q0 + u * stride;
             if (nq[u] <= 0) continue;
             const double v = wd_d2(nx, nq[u], wd_sqdiff(cx, cq[u]));
             if (q == yprev) dp = v;
-            if (wd_before(v, q, br, bi)) { br = v; bi = q; }
+            if (gs_before(v, q, br, bi)) { br = v; bi = q; }
         }
     }
     // wave -> workgroup (br, bi, dp are the same in every lane of a wave)
@@ -253,18 +237,13 @@ __global__ __launch_bounds__(WD_THREADS) void wd_step_kernel(WdArgs a) {
     __syncthreads();
     if (tid == 0) {
 #pragma unroll
-        for (int k = 1; k < WD_WAVES; ++k) {
-            if (wd_before(s_r[k], s_i[k], br, bi)) { br = s_r[k]; bi = s_i[k]; }
+        for (int k = 1; k < GS_WAVES; ++k) {
+            if (gs_before(s_r[k], s_i[k], br, bi)) { br = s_r[k]; bi = s_i[k]; }
             dp = fmax(dp, s_d[k]);
         }
-        // workgroup -> grid: write-through stores, drained, then the ticket
-        unsigned long long* mine = a.part + (size_t)WD_PART * blockIdx.x;
-        __hip_atomic_store(mine, (unsigned long long)__double_as_longlong(br), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 1, (unsigned long long)(unsigned)bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(mine + 2, (unsigned long long)__double_as_longlong(dp), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned t = __hip_atomic_fetch_add(&a.st->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = t == gridDim.x - 1;
+        // workgroup -> grid
+        const unsigned long long partial[3] = {gs_word(br), gs_word(bi), gs_word(dp)};
+        s_last = gs_post(a.part + (size_t)WD_PART * blockIdx.x, &a.st->ticket, partial);
     }
     __syncthreads();
     if (!s_last) return;
@@ -294,7 +273,7 @@ __global__ __launch_bounds__(WD_THREADS) void wd_step_kernel(WdArgs a) {
     const int na = a.size[ia], nb = a.size[ib];
     const int first = a.st->first;
     const double fs = (double)(na + nb);
-    if (tid < d) {          // (d <= 256 < WD_THREADS: a coordinate per thread, read and written by that thread alone)
+    if (tid < d) {          // (d <= 256 < GS_THREADS: a coordinate per thread, read and written by that thread alone)
         double* sa = a.S + (size_t)ia * d + tid;
         double* sb = a.S + (size_t)ib * d + tid;
         const double s = wd_add(*sa, *sb);
@@ -345,23 +324,8 @@ int dic_ward_linkage(const float* X, long ldx, int64_t N, int D, double* records
     a.n = (int)N; a.d = D;
     a.S = (double*)(ws + o.S); a.C = (double*)(ws + o.C); a.size = (int*)(ws + o.size); a.chain = (int*)(ws + o.chain);
     a.part = (unsigned long long*)(ws + o.part); a.st = (WdState*)(ws + o.state); a.rec = records;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute((const void*)wd_step_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WD_LDS_HOLD);
-        DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "ward_linkage: cannot reserve %d B of LDS: %s", WD_LDS_HOLD, hipGetErrorString(e));
-        attr_set = true;
-    }
     hipLaunchKernelGGL(wd_init_kernel, dim3((unsigned)min((N + 3) / 4, (int64_t)(8 * kNumCU))), dim3(256), 0, st, X, ldx, a);
-    const dim3 grid((unsigned)wd_blocks(N));
-    const long long steps = 3 * (N - 1);
-    for (long long s = 0; s < steps; ++s) {
-        hipLaunchKernelGGL(wd_step_kernel, grid, dim3(WD_THREADS), WD_LDS_HOLD, st, a);
-        if ((s & 4095) == 4095) {          // a stream that refuses launches is not fed the rest of them
-            const int rc = check_launch("ward_linkage");
-            if (rc) return rc;
-        }
-    }
-    return check_launch("ward_linkage");
+    return gs_enqueue<wd_step_kernel>("ward_linkage", a, (int*)nullptr, N, 3 * (N - 1), st);
 }
 
 }  // extern "C"

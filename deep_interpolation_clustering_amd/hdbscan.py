@@ -25,11 +25,10 @@ from __future__ import annotations
 import numbers
 
 import numpy as np
-import torch
 
-from . import _native as N
 from . import knn
 from .dbscan import MAX_DIM, _device_points
+from .optics import device_walk
 
 HIERARCHY_dtype = np.dtype([('left_node', np.intp), ('right_node', np.intp), ('value', np.float64), ('cluster_size', np.intp)])
 CONDENSED_dtype = np.dtype([('parent', np.intp), ('child', np.intp), ('value', np.float64), ('cluster_size', np.intp)])
@@ -51,20 +50,9 @@ def hdbscan_mst(X, min_samples, stats=None):
     if k > n:
         raise ValueError('min_samples (%d) must be at most the number of samples in X (%d)' % (k, n))
     x = _device_points(X)
-    d = x.shape[1]
     core = knn.kth_neighbor_distance(x, k, stats=stats)
-    L = N.lib()
-    dev = x.device
-    core_d = torch.as_tensor(core, device=dev)
-    ws = torch.empty(max(16, L.dic_hdbscan_workspace(n, d)), dtype=torch.uint8, device=dev)
-    ordering = torch.empty(n, dtype=torch.int32, device=dev)
-    reach = torch.empty(n, dtype=torch.float64, device=dev)
-    pred = torch.empty(n, dtype=torch.int32, device=dev)
-    N.check(L.dic_hdbscan_mst(N.ptr(x), x.stride(0), n, d, N.ptr(core_d), N.ptr(ordering), N.ptr(reach), N.ptr(pred), N.ptr(ws), ws.numel(), N.stream_of(x)),
-            'dic_hdbscan_mst')
-    if stats is not None:
-        stats['steps'] = n - 1
-    return ordering.cpu().numpy().astype(np.int64), core, reach.cpu().numpy(), pred.cpu().numpy().astype(np.int64)
+    ordering, reach, pred = device_walk(x, core, 'dic_hdbscan_workspace', 'dic_hdbscan_mst', stats=stats)
+    return ordering, core, reach, pred
 
 
 def single_linkage_tree(ordering, reach):

@@ -47,6 +47,25 @@ def _resolve_size(size, n, name):
     return int(size)
 
 
+def device_walk(x, core, workspace, entry, *params, stats=None):
+    """The walk OPTICS and HDBSCAN share (csrc/dic_gridstep.h), enqueued by the C entry point ``entry`` on a workspace sized by the C function
+    ``workspace``: ``x`` the device points (``_device_points``), ``core`` (N,) f64 numpy, ``params`` what ``entry`` takes between ``core`` and
+    ``ordering``.  Returns ``(ordering int64, reach f64, pred int64)``, numpy; ``stats['steps']`` receives the launches of the walk."""
+    L = N.lib()
+    n, d = x.shape
+    dev = x.device
+    core_d = torch.as_tensor(core, device=dev)
+    ws = torch.empty(max(16, getattr(L, workspace)(n, d)), dtype=torch.uint8, device=dev)
+    ordering = torch.empty(n, dtype=torch.int32, device=dev)
+    reach = torch.empty(n, dtype=torch.float64, device=dev)
+    pred = torch.empty(n, dtype=torch.int32, device=dev)
+    N.check(getattr(L, entry)(N.ptr(x), x.stride(0), n, d, N.ptr(core_d), *params, N.ptr(ordering), N.ptr(reach), N.ptr(pred), N.ptr(ws), ws.numel(),
+                              N.stream_of(x)), entry)
+    if stats is not None:
+        stats['steps'] = n - 1
+    return ordering.cpu().numpy().astype(np.int64), reach.cpu().numpy(), pred.cpu().numpy().astype(np.int64)
+
+
 def optics_graph(X, min_samples, max_eps=np.inf, stats=None):
     """``sklearn.cluster.compute_optics_graph`` (euclidean): ``(ordering int64, core_distances f64, reachability f64, predecessor int64)``, numpy, each (N,).
     ``X`` (numpy array or tensor, (N, D), D <= 256); a tensor on the device gives the same bits as the numpy array.  ``stats`` (a dict, optional) receives the
@@ -61,22 +80,11 @@ def optics_graph(X, min_samples, max_eps=np.inf, stats=None):
     if k > n:          # (a fraction of a tiny set: max(2, .) exceeds it -- sklearn fails in its neighbour query with this message)
         raise ValueError('Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %d' % (k, n))
     x = _device_points(X)
-    d = x.shape[1]
     core = knn.kth_neighbor_distance(x, k, stats=stats)
     core[core > max_eps] = np.inf
     core = around15(core)
-    L = N.lib()
-    dev = x.device
-    core_d = torch.as_tensor(core, device=dev)
-    ws = torch.empty(max(16, L.dic_optics_workspace(n, d)), dtype=torch.uint8, device=dev)
-    ordering = torch.empty(n, dtype=torch.int32, device=dev)
-    reach = torch.empty(n, dtype=torch.float64, device=dev)
-    pred = torch.empty(n, dtype=torch.int32, device=dev)
-    N.check(L.dic_optics_order(N.ptr(x), x.stride(0), n, d, N.ptr(core_d), max_eps, N.ptr(ordering), N.ptr(reach), N.ptr(pred), N.ptr(ws), ws.numel(),
-                               N.stream_of(x)), 'dic_optics_order')
-    if stats is not None:
-        stats['steps'] = n - 1
-    return ordering.cpu().numpy().astype(np.int64), core, reach.cpu().numpy(), pred.cpu().numpy().astype(np.int64)
+    ordering, reach, pred = device_walk(x, core, 'dic_optics_workspace', 'dic_optics_order', max_eps, stats=stats)
+    return ordering, core, reach, pred
 
 
 def cluster_optics_dbscan(*, reachability, core_distances, ordering, eps):

@@ -19,25 +19,16 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from deep_interpolation_clustering_amd import _native as N  # noqa: E402
 from deep_interpolation_clustering_amd import knn  # noqa: E402
 from deep_interpolation_clustering_amd.dbscan import _device_points  # noqa: E402
 from deep_interpolation_clustering_amd.hdbscan import condense_tree, hdbscan_mst, single_linkage_tree, tree_to_labels  # noqa: E402
+from deep_interpolation_clustering_amd.optics import device_walk  # noqa: E402
 from optics_bench import latents, sync_time  # noqa: E402
 
 
 def walk(x, core):
     """The N - 1 steps alone (the C entry point, as hdbscan_mst calls it)."""
-    L = N.lib()
-    n, d = x.shape
-    core_d = torch.as_tensor(core, device=x.device)
-    ws = torch.empty(L.dic_hdbscan_workspace(n, d), dtype=torch.uint8, device=x.device)
-    ordering = torch.empty(n, dtype=torch.int32, device=x.device)
-    pred = torch.empty(n, dtype=torch.int32, device=x.device)
-    reach = torch.empty(n, dtype=torch.float64, device=x.device)
-    N.check(L.dic_hdbscan_mst(N.ptr(x), x.stride(0), n, d, N.ptr(core_d), N.ptr(ordering), N.ptr(reach), N.ptr(pred), N.ptr(ws), ws.numel(), N.stream_of(x)),
-            'dic_hdbscan_mst')
-    return ordering, reach, pred
+    return device_walk(x, core, 'dic_hdbscan_workspace', 'dic_hdbscan_mst')
 
 
 def main():

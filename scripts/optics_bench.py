@@ -17,10 +17,9 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from deep_interpolation_clustering_amd import _native as N  # noqa: E402
 from deep_interpolation_clustering_amd import knn  # noqa: E402
 from deep_interpolation_clustering_amd.dbscan import _device_points  # noqa: E402
-from deep_interpolation_clustering_amd.optics import around15, cluster_optics_xi, optics_graph  # noqa: E402
+from deep_interpolation_clustering_amd.optics import around15, cluster_optics_xi, device_walk, optics_graph  # noqa: E402
 
 
 def latents(n, seed=0):
@@ -44,16 +43,7 @@ def sync_time(fn):
 
 def main_loop(x, core):
     """The N - 1 steps alone (the C entry point, as optics_graph calls it)."""
-    L = N.lib()
-    n, d = x.shape
-    core_d = torch.as_tensor(core, device=x.device)
-    ws = torch.empty(L.dic_optics_workspace(n, d), dtype=torch.uint8, device=x.device)
-    ordering = torch.empty(n, dtype=torch.int32, device=x.device)
-    pred = torch.empty(n, dtype=torch.int32, device=x.device)
-    reach = torch.empty(n, dtype=torch.float64, device=x.device)
-    N.check(L.dic_optics_order(N.ptr(x), x.stride(0), n, d, N.ptr(core_d), float('inf'), N.ptr(ordering), N.ptr(reach), N.ptr(pred), N.ptr(ws), ws.numel(),
-                               N.stream_of(x)), 'dic_optics_order')
-    return ordering, reach, pred
+    return device_walk(x, core, 'dic_optics_workspace', 'dic_optics_order', float('inf'))
 
 
 def main():

@@ -22,7 +22,7 @@ from deep_interpolation_clustering_amd import _native as N
 from deep_interpolation_clustering_amd import knn
 from deep_interpolation_clustering_amd.info import COHORTS
 from deep_interpolation_clustering_amd.hdbscan import HDBSCAN, hdbscan_mst, hdbscan_sizes, labelling_at_cut, single_linkage_tree, tree_to_labels
-from test_gpu_optics import _write_latents, dmat, matrix, points
+from test_gpu_optics import LINE_N, _write_latents, dmat, line, matrix, points
 
 pytestmark = pytest.mark.gpu
 
@@ -240,6 +240,22 @@ def test_duplicated_points_compare_exactly(k):
         assert np.all(core == 0.0) and (reach == 0.0).sum() == 500
         fit = HDBSCAN(min_cluster_size=2, min_samples=2).fit(X)          # lambda = inf at the zero weights: the extraction runs through
         assert fit.labels_.shape == (1000,) and np.isfinite(fit.probabilities_).all()
+
+
+def test_second_trip_of_the_row_loop_on_a_line():
+    # as in test_gpu_optics.py: more rows than one trip of the step's row loop takes, on the input whose walk is known in closed form
+    X, o_ord, o_reach, o_pred = line(300)
+    ordering, core, reach, pred, _ = oracle_mst(dmat(X), 2)
+    assert np.all(core == 1.0)
+    np.testing.assert_array_equal(ordering, o_ord)
+    np.testing.assert_array_equal(reach, o_reach)
+    np.testing.assert_array_equal(pred, o_pred)
+    X, o_ord, o_reach, o_pred = line(LINE_N)
+    ordering, core, reach, pred = hdbscan_mst(X, 2)
+    assert np.all(core == 1.0)
+    np.testing.assert_array_equal(ordering, o_ord)
+    np.testing.assert_array_equal(reach, o_reach)
+    np.testing.assert_array_equal(pred, o_pred)
 
 
 def _abi_call(x, core):

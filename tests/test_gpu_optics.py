@@ -229,6 +229,45 @@ def test_duplicated_points_compare_exactly(k):
         assert np.all(core == 0.0) and (reach == 0.0).sum() == 500
 
 
+LINE_N = 16640          # 256 workgroups x 16 waves x 4 rows in flight = 16 384 rows per trip of a step's row loop: the smallest multiple of 256 above it
+
+
+@functools.lru_cache(maxsize=None)
+def line(n):
+    """Points whose walk has a closed form: point j sits at ``(pos[j], 0, 0, 0)``, ``pos`` a seeded permutation of 0..n-1 with ``pos[0] = 0`` -- integers below
+    2^24, so every coordinate and distance is exact.  With min_samples = 2 every core distance is 1.0, and OPTICS and Prim both walk the line left to right with
+    no tie to break: the point at position i + 1 is reached at exactly 1.0, every other one at 2.0 or more.  ``(X, ordering, reach, pred)``, read-only."""
+    rng = np.random.default_rng(16)
+    pos = np.concatenate([[0], 1 + rng.permutation(n - 1)])
+    X = np.zeros((n, 4), dtype=np.float32)
+    X[:, 0] = pos
+    ordering = np.argsort(pos)          # the point at position i
+    pred = np.full(n, -1, dtype=np.int64)
+    pred[ordering[1:]] = ordering[:-1]
+    reach = np.ones(n)
+    reach[0] = np.inf
+    for a in (X, ordering, reach, pred):
+        a.setflags(write=False)
+    return X, ordering, reach, pred
+
+
+def test_second_trip_of_the_row_loop_on_a_line():
+    # the oracle cases end at 6000 rows, one trip of the row loop; the matrix oracle is O(N^2), so the long input is one whose answer is known in closed form,
+    # which the oracle confirms at 300 points first
+    X, o_ord, o_reach, o_pred = line(300)
+    ordering, core, reach, pred, _ = oracle_optics(dmat(X), 2)
+    assert np.all(core == 1.0)
+    np.testing.assert_array_equal(ordering, o_ord)
+    np.testing.assert_array_equal(reach, o_reach)
+    np.testing.assert_array_equal(pred, o_pred)
+    X, o_ord, o_reach, o_pred = line(LINE_N)
+    ordering, core, reach, pred = optics_graph(X, 2)
+    assert np.all(core == 1.0)
+    np.testing.assert_array_equal(ordering, o_ord)
+    np.testing.assert_array_equal(reach, o_reach)
+    np.testing.assert_array_equal(pred, o_pred)
+
+
 def test_small_sets_and_min_samples_forms():
     rng = np.random.default_rng(2)
     X2 = rng.normal(0, 1, (2, 4)).astype(np.float32)
