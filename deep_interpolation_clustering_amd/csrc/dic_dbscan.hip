@@ -1,32 +1,20 @@
 // DBSCAN on the matrix cores (p2_clustering_optK.py:82-85,90-168, p4_clustering_final.py:181-236): upstream builds pairwise_distances(X) (N x N f32, 22.5 GB
 // at 75 000 points) and runs DBSCAN(eps, min_samples, metric='precomputed') on it.  Here every pair pass recomputes the distances tile by tile, nothing N x N is
-// ever stored.
+// ever stored: the planes, the tile loop and the error bound B0 = 2^-12 (n_i + nmax_J) of its approximate d^2 (call it a_ij) are dic_pairtile.h's; this file is
+// the two epilogues that decide on it, the exact recheck and the label bookkeeping.
 //
 // NEIGHBOUR RULE (sklearn's, bit for bit): (i, j) are neighbours for eps e iff f32(d^2_ij) <= t_e, where d^2 is the exact squared distance of the f32 points and
 // t_e (f32) is the largest float s with np.sqrt(np.float32(s)) <= eps under NumPy's promotion of the caller's eps object (dbscan.py finds it on the host).  The
 // self pair counts (d = 0).
 //
-// PAIR PASSES.  The machine of dic_intra.hip's intra_x3_kernel<ROWS>: one persistent 8-wave workgroup per CU walks a contiguous range of the (I, J) list of
-// 256 x 256 point-pair tiles (ALL ordered block pairs, row-major), both operands' 32-column slabs streamed through LDS-DMA rings; d^2 = n_i + n_j - 2 v_i . v_j
-// is one inner product of 288-column augmented rows, v = x - mean (f32), every coordinate as bf16 hi + lo with the products hi.hi + lo.hi + hi.lo, the f32 norms
-// n = sum v^2 as three exact bf16 pieces.  Lane = point i, registers = points j: a lane's per-i results stay in registers while its workgroup's range stays on
-// one row block I and are flushed (integer atomics: exact, order-free) when I changes.
-//
-// ERROR BOUND of the approximate d^2 (call it a_ij) against the exact d^2_ij of the f32 points, u = 2^-24:
-//   (1) v = fl(x - mean): each coordinate of v_i - v_j is off by <= u (|v_ik| + |v_jk|), so |d_v^2 - d^2| <= 2u (|v_i| + |v_j|)^2 (1 + u) <= 4.1u (n_i + n_j).
-//   (2) the split: h = bf16(v), |v - h| <= 2^-8 |v|; l = bf16(v - h) (v - h exact in f32), |v - h - l| <= 2^-16 |v|.  The dropped part of a product a.b is
-//       l_a l_b + r_a b + (h_a + l_a) r_b, <= 3.1 * 2^-16 |a| |b|; b = -2 v_j splits exactly as -2 (h, l), so -2 v_i . v_j is off by
-//       <= 6.2 * 2^-16 sum_k |v_ik| |v_jk| <= 3.1 * 2^-16 (n_i + n_j).
-//   (3) f32 accumulation: 288 / 16 * 3 = 54 chained MFMAs of 16 exact products each, at most 54 * 16 = 864 roundings in sequence, each of
-//       sum |terms| <= (n_i + n_j) + 2 * (1 + 2^-7) sum |v_ik v_jk| <= 2.02 (n_i + n_j):  <= 864 u * 2.02 (n_i + n_j) <= 2^-13.2 (n_i + n_j).
-//   (4) the norms' own f32 rounding (4 fmas + 6 shuffle adds): <= 10u (n_i + n_j).
-//   Together |a_ij - d^2_ij| < (0.11 + 0.19 + 0.43 + 0.01) 2^-12 (n_i + n_j) < B0 = 2^-12 (n_i + nmax_J), nmax_J the largest n of j's 256-row block.
-// A lane forms y = fl(a + B0) and z = fl(a - B0) and decides the pair itself when
+// A lane forms y = fl(a + B0) and z = fl(a - B0), u = 2^-24, and decides the pair itself when
 //   y <= tl_e = t_e (1 - 2^-20)   =>  d^2 <= a + B0 <= y (1 + u) < t_e               (a neighbour), or
 //   z >  th_e = t_e (1 + 2^-20)   =>  d^2 >= a - B0 >= z (1 - u) > t_e + ulp(t_e)    (not one: its f32 rounding stays above t_e).
 // The margin 2^-20 t_e also covers the difference between the exact d^2 and sklearn's f64 norm form (~2^-52 of |x_i|^2 + |x_j|^2), for points with
 // |x|^2 < 2^30 t_e.  Every other pair (a BAND pair, in the band of some e) is appended to a device list and rechecked exactly: f64 difference form over the f32
 // coordinates (each term exact, 256 of them summed in f64), rounded to f32, compared with every t_e.
+// The 256 padding points behind the last one present the norm PT_PAD_NORM = 2^120 as operand j: their y and z lie above every tl_e / th_e, so they are neither
+// counted nor put in a band and no pair is masked by its column index.  That needs thresholds well below the norm: t_e < DB_MAX_THRESHOLD = 2^100 (eps < 2^50).
 //
 // COUNTS (one pass, all eps): counts[e][i] = |N_eps(i)|; a band pair contributes nothing in the tile (for no e) and its exact neighbour mask from the recheck.
 // COMPONENTS of the core graph, per eps: label passes L (init L[i] = i), each ONE launch of the tile kernel + one of the band list + one pointer jump:
@@ -38,101 +26,21 @@
 // that changes nothing -- no label is written while it runs, so those minima are over the final roots: the smallest cluster id among i's core neighbours
 // (sklearn's _dbscan_inner labels a border point from the first cluster that reaches it, and clusters are numbered by their smallest core index).
 // No workgroup waits for another inside a kernel: the kernel boundaries are the only barriers.
-#include "dic_common.h"
+#include <type_traits>
+#include "dic_pairtile.h"
 
 namespace dic {
 
-typedef __bf16 dbf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 dbf16x4 __attribute__((ext_vector_type(4)));
-typedef float df32x16 __attribute__((ext_vector_type(16)));
-typedef float df32x4 __attribute__((ext_vector_type(4)));
-typedef int di32x4 __attribute__((ext_vector_type(4)));
+typedef pi32x4 di32x4;
 
-constexpr int DB_D = 256;                              // coordinates (narrower inputs are zero-padded by the caller to a multiple of 4)
-constexpr int DB_LD = 288;                             // columns of an augmented row
-constexpr int DB_T = 256;                              // points per tile edge
-constexpr int DB_K = 32;                               // columns per slab
-constexpr int DB_ROWB = DB_K * 2;                      // 64 B
-constexpr int DB_PLANE = DB_T * DB_ROWB;               // 16 KB: one plane of a slab
-constexpr int DB_SLOT = 2 * DB_PLANE;                  // 32 KB: hi | lo
-constexpr int DB_SLABS = DB_LD / DB_K;                 // 9
-constexpr int DB_NI = 3, DB_NJ = 2;                    // ring depths of the two operands
-constexpr int DB_LDS = (DB_NI + DB_NJ) * DB_SLOT;      // 163 840 B
 constexpr int DB_MAX_EPS = 16;
 constexpr int DB_NONE = 0x7fffffff;
-static_assert(DB_LDS <= 160 * 1024, "dbscan: LDS budget");
+constexpr float DB_MAX_THRESHOLD = 0x1p100f;           // thresholds stay this far below PT_PAD_NORM
 
-__device__ __forceinline__ void dbdma16(const void* sbase, unsigned voff, unsigned lds_dst) {
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(lds_dst) : "memory");
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------------------
-// Augmented rows relative to one centre, and the f32 norms.  One wave per point: lane l holds coordinates 4 l .. 4 l + 3.
-__global__ __launch_bounds__(256) void db_prep_kernel(const float* X, long ldx, const float* mu, int n, int d, __bf16* pa, __bf16* pb, long plane, float* nrm_out) {
-    const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (row >= n) return;
-    const int col = 4 * lane;
-    df32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (col < d) {
-        const df32x4 x = *reinterpret_cast<const df32x4*>(X + (size_t)row * ldx + col);
-        const df32x4 m = *reinterpret_cast<const df32x4*>(mu + col);
-        v = x - m;
-    }
-    float nrm = fmaf(v[0], v[0], fmaf(v[1], v[1], fmaf(v[2], v[2], v[3] * v[3])));
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) nrm += __shfl_xor(nrm, o);
-    dbf16x4 ah, al, bh, bl;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-        const __bf16 h = (__bf16)v[e];
-        const __bf16 l = (__bf16)(v[e] - (float)h);
-        ah[e] = h; al[e] = l;
-        bh[e] = (__bf16)(-2.f * (float)h); bl[e] = (__bf16)(-2.f * (float)l);          // exact
-    }
-    const size_t at = (size_t)row * DB_LD + col;
-    *reinterpret_cast<dbf16x4*>(pa + at) = ah;
-    *reinterpret_cast<dbf16x4*>(pa + plane + at) = al;
-    *reinterpret_cast<dbf16x4*>(pb + at) = bh;
-    *reinterpret_cast<dbf16x4*>(pb + plane + at) = bl;
-    if (lane < 8) {                                     // columns 256 + 4 lane ..: [n n n 1 | 1 1 0 0 | 0 ..] and [1 1 1 n | n n 0 0 | 0 ..]
-        const __bf16 n0 = (__bf16)nrm;
-        const float r1 = nrm - (float)n0;
-        const __bf16 n1 = (__bf16)r1;
-        const __bf16 n2 = (__bf16)(r1 - (float)n1);
-        const __bf16 one = (__bf16)1.f, z = (__bf16)0.f;
-        dbf16x4 ea = {z, z, z, z}, eb = {z, z, z, z};
-        if (lane == 0) { ea = dbf16x4{n0, n1, n2, one}; eb = dbf16x4{one, one, one, n0}; }
-        if (lane == 1) { ea = dbf16x4{one, one, z, z}; eb = dbf16x4{n1, n2, z, z}; }
-        const size_t et = (size_t)row * DB_LD + DB_D + 4 * lane;
-        const dbf16x4 zz = {z, z, z, z};
-        *reinterpret_cast<dbf16x4*>(pa + et) = ea;
-        *reinterpret_cast<dbf16x4*>(pa + plane + et) = zz;
-        *reinterpret_cast<dbf16x4*>(pb + et) = eb;
-        *reinterpret_cast<dbf16x4*>(pb + plane + et) = zz;
-    }
-    if (lane == 0) nrm_out[row] = nrm;
-}
-
-// largest norm of every 256-row block (norms are >= 0; rows past n count 0)
-__global__ __launch_bounds__(256) void db_block_max_kernel(const float* nrm, int n, float* bmax) {
-    __shared__ float part[4];
-    const int i = blockIdx.x * DB_T + threadIdx.x;
-    float v = i < n ? nrm[i] : 0.f;
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) bmax[blockIdx.x] = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------------------
 struct DbThresholds { float tl[DB_MAX_EPS], th[DB_MAX_EPS], t[DB_MAX_EPS]; };
 
 struct DbTileArgs {
-    const __bf16* pa; const __bf16* pb; long plane;
-    const float* nrm; const float* bmax;
-    int n, nblk; long long ntiles;
+    PtPairArgs p;
     DbThresholds thr; int n_eps;
     // counts
     int32_t* counts; di32x4* band; long long cap; unsigned long long* band_count;
@@ -140,244 +48,160 @@ struct DbTileArgs {
     const int32_t* cnt_e; int min_samples; int32_t* L; int32_t* border; int32_t* changed;
 };
 
-// MODE 0: counts of every eps (NE thresholds, NE >= n_eps; unused ones never match) + the band list.  MODE 1: one label pass of eps 0 of thr.
-template <int MODE, int NE>
-__global__ __launch_bounds__(512, 1) void db_tile_kernel(DbTileArgs a) {
-    extern __shared__ __align__(16) unsigned char dsm[];
-    const int tid = threadIdx.x, lane = tid & 63, hh = lane >> 5, l31 = lane & 31;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6), wm = w & 3, wn = w >> 2;
-    const long long nch = gridDim.x;
-    const long long per = (a.ntiles + nch - 1) / nch;
-    const long long first = (long long)blockIdx.x * per;
-    const long long my_tiles = max(0LL, min(per, a.ntiles - first));
-    const long long S = my_tiles * DB_SLABS;
-    if (S == 0) return;
-    const unsigned lds0 = (unsigned)(size_t)((__attribute__((address_space(3))) unsigned char*)dsm);
-    const unsigned ldsI = lds0, ldsJ = lds0 + DB_NI * DB_SLOT;
-    const unsigned v_dma = (unsigned)(lane >> 2) * (DB_LD * 2) + (unsigned)(((lane & 3) ^ ((lane >> 4) & 3)) * 16);
-    // tile t of the range: (first row of I, first row of J), row-major over the block pairs
-    auto tile = [&](long long i) {
-        const long long t = first + min(i, my_tiles - 1);
-        const int bi = (int)(t / a.nblk), bj = (int)(t - (long long)bi * a.nblk);
-        di32x4 r;
-        r[0] = __builtin_amdgcn_readfirstlane(bi * DB_T);
-        r[1] = __builtin_amdgcn_readfirstlane(bj * DB_T);
-        r[2] = 0; r[3] = 0;
-        return r;
-    };
-    di32x4 e_cur = tile(0), e_nxt = tile(1), e_prev = e_cur;
-    long long cur_tile = 0;
-    auto issue = [&](const __bf16* mat, int row0, int ks, unsigned dst) {
-        const __bf16* src = mat + (size_t)row0 * DB_LD + ks * DB_K;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int c = w + 8 * j, pl = c >> 4, rg = c & 15;
-            const uint64_t p = (uint64_t)(src + (size_t)pl * a.plane + (size_t)(16 * rg) * DB_LD);          // (uniform: keep the base in scalar registers)
-            const uint64_t q = ((uint64_t)__builtin_amdgcn_readfirstlane((unsigned)(p >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((unsigned)p);
-            dbdma16((const void*)q, v_dma, __builtin_amdgcn_readfirstlane(dst + pl * DB_PLANE + rg * 1024));
-        }
-    };
-    auto issue_i = [&](long long s) { issue(a.pa, s / DB_SLABS == cur_tile ? e_cur[0] : e_nxt[0], (int)(s % DB_SLABS), ldsI + (int)(s % DB_NI) * DB_SLOT); };
-    auto issue_j = [&](long long s) { issue(a.pb, s / DB_SLABS == cur_tile ? e_cur[1] : e_nxt[1], (int)(s % DB_SLABS), ldsJ + (int)(s % DB_NJ) * DB_SLOT); };
-    const int sw = (l31 >> 2) & 3;
-    int poff[DB_K / 16];
-#pragma unroll
-    for (int kk = 0; kk < DB_K / 16; ++kk) poff[kk] = ((2 * kk + hh) ^ sw) * 16;
-    const int j_row = (128 * wn + l31) * DB_ROWB;
-    const int i_row = (64 * wm + l31) * DB_ROWB;
-
-#pragma unroll
-    for (int it = 1 - DB_NI; it < 0; ++it) {
-        if (it + DB_NJ - 1 >= 0 && it + DB_NJ - 1 < S) issue_j(it + DB_NJ - 1);
-        if (it + DB_NI - 1 < S) issue_i(it + DB_NI - 1);
-    }
-    df32x16 acc[4][2];
-    // per-lane state of the current row block I
+// Counting epilogue: counts of every eps (NE thresholds, NE >= n_eps; unused ones never match) + the band list.
+template <int NE>
+struct DbCount {
+    const DbTileArgs& a;
+    const PtLane ln;
     int cur_i = -1;
     float ni[2] = {0.f, 0.f};
     int cnt[2][NE];
-    int mn[2] = {DB_NONE, DB_NONE};
-#pragma unroll
-    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-        for (int e = 0; e < NE; ++e) cnt[mb][e] = 0;
 
-    auto flush = [&]() {
+    __device__ __forceinline__ DbCount(const DbTileArgs& args) : a(args), ln() {
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb)
+#pragma unroll
+            for (int e = 0; e < NE; ++e) cnt[mb][e] = 0;
+    }
+    __device__ __forceinline__ void flush() {
         if (cur_i < 0) return;
 #pragma unroll
         for (int mb = 0; mb < 2; ++mb) {
-            const int gi = cur_i + 64 * wm + 32 * mb + l31;
-            if constexpr (MODE == 0) {
+            const int gi = ln.row(cur_i, mb);
 #pragma unroll
-                for (int e = 0; e < NE; ++e) {
-                    const int v = cnt[mb][e] + __shfl_xor(cnt[mb][e], 32);
-                    if (hh == 0 && gi < a.n && e < a.n_eps && v) atomicAdd(a.counts + (size_t)e * a.n + gi, v);
-                    cnt[mb][e] = 0;
-                }
-            } else {
-                const int m = min(mn[mb], __shfl_xor(mn[mb], 32));
-                if (hh == 0 && gi < a.n && m != DB_NONE) {
-                    if (a.cnt_e[gi] >= a.min_samples) {
-                        const int li = a.L[gi];
-                        if (m < li) {
-                            atomicMin(a.L + li, m);
-                            atomicMin(a.L + gi, m);
-                            *a.changed = 1;
-                        }
-                    } else {
-                        atomicMin(a.border + gi, m);
-                    }
-                }
-                mn[mb] = DB_NONE;
+            for (int e = 0; e < NE; ++e) {
+                const int v = cnt[mb][e] + __shfl_xor(cnt[mb][e], 32);
+                if (ln.hh == 0 && gi < a.p.n && e < a.n_eps && v) atomicAdd(a.counts + (size_t)e * a.p.n + gi, v);
+                cnt[mb][e] = 0;
             }
         }
-    };
-    auto finish = [&](di32x4 e) {
-        const int I0 = e[0], J0 = e[1];
+    }
+    __device__ __forceinline__ void finish(int I0, int J0, const pf32x16 (&acc)[4][2]) {
         if (I0 != cur_i) {
             flush();
             cur_i = I0;
 #pragma unroll
-            for (int mb = 0; mb < 2; ++mb) ni[mb] = a.nrm[I0 + 64 * wm + 32 * mb + l31];          // (padding rows hold 0)
+            for (int mb = 0; mb < 2; ++mb) ni[mb] = a.p.nrm[ln.row(I0, mb)];          // (padding rows hold 0)
         }
-        const float bm = a.bmax[J0 / DB_T];
-        const int jw = J0 + 128 * wn;
-        if constexpr (MODE == 0) {
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) {
-                const int gi = I0 + 64 * wm + 32 * mb + l31;
-                const bool iv = gi < a.n;
-                const float b0 = (ni[mb] + bm) * 0x1p-12f;
-                unsigned bits[2] = {0u, 0u};
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) {
-                        const int gj = jw + 32 * nb + 4 * hh + (k & 3) + 8 * (k >> 2);
-                        const bool ok = iv && gj < a.n;
-                        const float d2 = acc[nb][mb][k];
-                        const float y = ok ? d2 + b0 : __builtin_inff();
-                        const float z = ok ? d2 - b0 : __builtin_inff();
-                        bool inb = false;
-#pragma unroll
-                        for (int q = 0; q < NE; ++q) inb |= (y > a.thr.tl[q]) & (z <= a.thr.th[q]);
-#pragma unroll
-                        for (int q = 0; q < NE; ++q) cnt[mb][q] += (int)((y <= a.thr.tl[q]) & !inb);
-                        bits[nb >> 1] |= inb ? (1u << (16 * (nb & 1) + k)) : 0u;
-                    }
-                const int nbits = __builtin_popcount(bits[0]) + __builtin_popcount(bits[1]);
-                if (nbits) {
-                    unsigned long long base = atomicAdd(a.band_count, (unsigned long long)nbits);
-                    for (int h = 0; h < 2; ++h) {
-                        unsigned b = bits[h];
-                        while (b) {
-                            const int p = __builtin_ctz(b);
-                            b &= b - 1;
-                            const int nb = 2 * h + (p >> 4), k = p & 15;
-                            const int gj = jw + 32 * nb + 4 * hh + (k & 3) + 8 * (k >> 2);
-                            if (base < (unsigned long long)a.cap) {
-                                di32x4 ent;
-                                ent[0] = gi; ent[1] = gj; ent[2] = 0; ent[3] = 0;
-                                a.band[base] = ent;
-                            }
-                            ++base;
-                        }
-                    }
-                }
-            }
-        } else {
-            // labels of the 128 points j of this wave's half of the tile (DB_NONE: not a core point, or past the end): lane l holds j = jw + l and jw + 64 + l
-            int lc[2];
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int j = jw + 64 * h + lane;
-                lc[h] = (j < a.n && a.cnt_e[j] >= a.min_samples) ? a.L[j] : DB_NONE;
-            }
-            const float tl = a.thr.tl[0];
-            float b0[2];
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) b0[mb] = (ni[mb] + bm) * 0x1p-12f;
+        const float bm = a.p.bmax[J0 / PT_T];
+        // the two rows of the lane, the row index a compile-time constant: as a `#pragma unroll` loop over mb this body was left rolled at NE = 16, which
+        // turned cnt[mb][q] into a run-time-indexed array in scratch (5 x the time of the pass)
+        auto rows = [&](auto MB) {
+            constexpr int mb = decltype(MB)::value;
+            const int gi = ln.row(I0, mb);
+            const bool iv = gi < a.p.n;          // (a padding row i counts what it likes: never flushed; but it must not reach the band list)
+            const float b0 = (ni[mb] + bm) * 0x1p-12f;
+            unsigned bits[2] = {0u, 0u};
 #pragma unroll
             for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
-                    const int jl = 32 * (nb & 1) + 4 * hh + (k & 3) + 8 * (k >> 2);
-                    const int v = __shfl(lc[nb >> 1], jl);
+                    const float d2 = acc[nb][mb][k];          // (a padding point j: PT_PAD_NORM, above every tl and th)
+                    const float y = d2 + b0, z = d2 - b0;
+                    bool inb = false;
 #pragma unroll
-                    for (int mb = 0; mb < 2; ++mb) {
-                        const float y = acc[nb][mb][k] + b0[mb];
-                        mn[mb] = min(mn[mb], y <= tl ? v : DB_NONE);
+                    for (int q = 0; q < NE; ++q) inb |= (y > a.thr.tl[q]) & (z <= a.thr.th[q]);
+#pragma unroll
+                    for (int q = 0; q < NE; ++q) cnt[mb][q] += (int)((y <= a.thr.tl[q]) & !inb);
+                    bits[nb >> 1] |= (iv && inb) ? (1u << (16 * (nb & 1) + k)) : 0u;
+                }
+            const int nbits = __builtin_popcount(bits[0]) + __builtin_popcount(bits[1]);
+            if (nbits) {
+                unsigned long long base = atomicAdd(a.band_count, (unsigned long long)nbits);
+                for (int h = 0; h < 2; ++h) {
+                    unsigned b = bits[h];
+                    while (b) {
+                        const int p = __builtin_ctz(b);
+                        b &= b - 1;
+                        if (base < (unsigned long long)a.cap) {
+                            di32x4 ent;
+                            ent[0] = gi; ent[1] = ln.col(J0, 2 * h + (p >> 4), p & 15); ent[2] = 0; ent[3] = 0;
+                            a.band[base] = ent;
+                        }
+                        ++base;
                     }
                 }
-        }
-    };
-    for (long long s = 0; s < S; ++s) {
-        const int ks = (int)(s % DB_SLABS);
-        if (ks == 0 && s > 0) {
-            e_prev = e_cur;
-            e_cur = e_nxt;
-            ++cur_tile;
-            e_nxt = tile(cur_tile + 1);
-        }
-        if (S - 1 - s >= DB_NI - 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        const unsigned char* A = dsm + DB_NI * DB_SLOT + (int)(s % DB_NJ) * DB_SLOT + j_row;
-        const unsigned char* Bm = dsm + (int)(s % DB_NI) * DB_SLOT + i_row;
-        dbf16x8 ah[2][4], bh[2][2], al[4], bl[2];
-        auto load_hi = [&](int kk, int set) {
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) bh[set][mb] = *reinterpret_cast<const dbf16x8*>(Bm + mb * 32 * DB_ROWB + poff[kk]);
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb) ah[set][nb] = *reinterpret_cast<const dbf16x8*>(A + nb * 32 * DB_ROWB + poff[kk]);
-        };
-        auto load_lo = [&](int kk) {
-#pragma unroll
-            for (int mb = 0; mb < 2; ++mb) bl[mb] = *reinterpret_cast<const dbf16x8*>(Bm + DB_PLANE + mb * 32 * DB_ROWB + poff[kk]);
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb) al[nb] = *reinterpret_cast<const dbf16x8*>(A + DB_PLANE + nb * 32 * DB_ROWB + poff[kk]);
-        };
-        load_hi(0, 0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (s + DB_NJ - 1 < S) issue_j(s + DB_NJ - 1);
-        if (s + DB_NI - 1 < S) issue_i(s + DB_NI - 1);
-        __builtin_amdgcn_sched_barrier(0);
-        if (ks == 0) {
-            if (s > 0) finish(e_prev);
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                    for (int k = 0; k < 16; ++k) acc[nb][mb][k] = 0.f;
-        }
-        const bool coords = ks < DB_D / DB_K;
-#pragma unroll
-        for (int kk = 0; kk < DB_K / 16; ++kk) {
-            if (coords) load_lo(kk);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb) acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk & 1][nb], bh[kk & 1][mb], acc[nb][mb], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kk + 1 < DB_K / 16) load_hi(kk + 1, (kk + 1) & 1);
-            __builtin_amdgcn_sched_barrier(0);
-            if (coords) {
-#pragma unroll
-                for (int nb = 0; nb < 4; ++nb)
-#pragma unroll
-                    for (int mb = 0; mb < 2; ++mb) {
-                        acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[nb], bh[kk & 1][mb], acc[nb][mb], 0, 0, 0);
-                        acc[nb][mb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[kk & 1][nb], bl[mb], acc[nb][mb], 0, 0, 0);
-                    }
             }
-            __builtin_amdgcn_sched_barrier(0);
+        };
+        rows(std::integral_constant<int, 0>{});
+        rows(std::integral_constant<int, 1>{});
+    }
+};
+
+// Label epilogue: one label pass of eps 0 of thr.
+struct DbLabel {
+    const DbTileArgs& a;
+    const PtLane ln;
+    int cur_i = -1;
+    float ni[2] = {0.f, 0.f};
+    int mn[2] = {DB_NONE, DB_NONE};
+
+    __device__ __forceinline__ DbLabel(const DbTileArgs& args) : a(args), ln() {}
+    __device__ __forceinline__ void flush() {
+        if (cur_i < 0) return;
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) {
+            const int gi = ln.row(cur_i, mb);
+            const int m = min(mn[mb], __shfl_xor(mn[mb], 32));
+            if (ln.hh == 0 && gi < a.p.n && m != DB_NONE) {
+                if (a.cnt_e[gi] >= a.min_samples) {
+                    const int li = a.L[gi];
+                    if (m < li) {
+                        atomicMin(a.L + li, m);
+                        atomicMin(a.L + gi, m);
+                        *a.changed = 1;
+                    }
+                } else {
+                    atomicMin(a.border + gi, m);
+                }
+            }
+            mn[mb] = DB_NONE;
         }
     }
-    finish(e_cur);
-    flush();
+    __device__ __forceinline__ void finish(int I0, int J0, const pf32x16 (&acc)[4][2]) {
+        if (I0 != cur_i) {
+            flush();
+            cur_i = I0;
+#pragma unroll
+            for (int mb = 0; mb < 2; ++mb) ni[mb] = a.p.nrm[ln.row(I0, mb)];          // (padding rows hold 0)
+        }
+        const float bm = a.p.bmax[J0 / PT_T];
+        // labels of the 128 points j of this wave's half of the tile (DB_NONE: not a core point, or past the end): lane l holds j = jw + l and jw + 64 + l
+        const int jw = J0 + 128 * ln.wn;
+        int lc[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = jw + 64 * h + ln.lane;
+            lc[h] = (j < a.p.n && a.cnt_e[j] >= a.min_samples) ? a.L[j] : DB_NONE;
+        }
+        const float tl = a.thr.tl[0];
+        float b0[2];
+#pragma unroll
+        for (int mb = 0; mb < 2; ++mb) b0[mb] = (ni[mb] + bm) * 0x1p-12f;
+#pragma unroll
+        for (int nb = 0; nb < 4; ++nb)
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const int jl = 32 * (nb & 1) + 4 * ln.hh + (k & 3) + 8 * (k >> 2);
+                const int v = __shfl(lc[nb >> 1], jl);
+#pragma unroll
+                for (int mb = 0; mb < 2; ++mb) {
+                    const float y = acc[nb][mb][k] + b0[mb];
+                    mn[mb] = min(mn[mb], y <= tl ? v : DB_NONE);
+                }
+            }
+    }
+};
+
+template <int NE>
+__global__ __launch_bounds__(512, 1) void db_count_kernel(DbTileArgs a) {
+    DbCount<NE> epi(a);
+    pt_pair_pass(a.p, epi);
+}
+
+__global__ __launch_bounds__(512, 1) void db_label_kernel(DbTileArgs a) {
+    DbLabel epi(a);
+    pt_pair_pass(a.p, epi);
 }
 
 // Band pairs, exactly: one wave per entry, f64 difference form over the f32 coordinates; entry .z = the neighbour mask over the eps; counts += it.
@@ -439,49 +263,11 @@ __global__ __launch_bounds__(256) void db_jump_kernel(int32_t* L, int n) {
     L[i] = l;
 }
 
-// ------------------------------------------------------------------------------------------------------------------------------------------
-struct DbLayout { size_t pa, pb, nrm, bmax, count, total; };
-
-static DbLayout db_layout(int64_t N) {
-    DbLayout o;
-    const size_t plane = (size_t)(N + DB_T) * DB_LD * sizeof(__bf16);
-    const size_t nblk = (size_t)((N + DB_T - 1) / DB_T);
-    o.pa = 0;
-    o.pb = o.pa + align_up(2 * plane, 256);
-    o.nrm = o.pb + align_up(2 * plane, 256);
-    o.bmax = o.nrm + align_up((size_t)(N + DB_T) * sizeof(float), 256);
-    o.count = o.bmax + align_up(nblk * sizeof(float), 256);
-    o.total = o.count + 256;
-    return o;
-}
-
 static int db_reserve_lds() {
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[] = {(const void*)db_tile_kernel<0, 1>, (const void*)db_tile_kernel<0, 4>, (const void*)db_tile_kernel<0, 10>,
-                             (const void*)db_tile_kernel<0, 16>, (const void*)db_tile_kernel<1, 1>};
-        for (const void* f : fns) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, DB_LDS);
-            DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "dbscan: cannot reserve %d B of LDS: %s", DB_LDS, hipGetErrorString(e));
-        }
-        attr_set = true;
-    }
-    return DIC_OK;
+    static bool done = false;
+    return pt_reserve_lds(done, {(const void*)db_count_kernel<1>, (const void*)db_count_kernel<4>, (const void*)db_count_kernel<10>,
+                                 (const void*)db_count_kernel<16>, (const void*)db_label_kernel}, "dbscan");
 }
-
-static void db_fill_tile_args(DbTileArgs& t, unsigned char* ws, int64_t N) {
-    const DbLayout o = db_layout(N);
-    t.pa = (const __bf16*)(ws + o.pa);
-    t.pb = (const __bf16*)(ws + o.pb);
-    t.plane = (long)((N + DB_T) * DB_LD);
-    t.nrm = (const float*)(ws + o.nrm);
-    t.bmax = (const float*)(ws + o.bmax);
-    t.n = (int)N;
-    t.nblk = (int)((N + DB_T - 1) / DB_T);
-    t.ntiles = (long long)t.nblk * t.nblk;
-}
-
-static unsigned db_grid(long long ntiles) { return (unsigned)max(1LL, min(ntiles, (long long)kNumCU)); }
 
 static void db_margins(float t, float& tl, float& th) {
     tl = t * (1.f - 0x1p-20f);
@@ -495,47 +281,37 @@ using namespace dic;
 extern "C" {
 
 size_t dic_dbscan_workspace(int64_t N, int D) {
-    if (N <= 0 || N >= (1LL << 30) || D <= 0 || D > DB_D) return 0;
-    return db_layout(N).total;
+    if (N <= 0 || N >= (1LL << 30) || D <= 0 || D > PT_D) return 0;
+    return pt_layout(N).total;
 }
 
 int dic_dbscan_counts(const float* X, long ldx, const float* centre, int64_t N, int D, const float* thresholds, int n_eps, int32_t* counts, int32_t* band,
                       int64_t capacity, int64_t* n_band, void* workspace, size_t workspace_bytes, dic_stream_t stream) {
     DIC_REQUIRE(N > 0 && D > 0 && ldx >= D && n_eps > 0 && capacity >= 0, DIC_ERR_INVALID_ARG, "dbscan_counts: N=%lld D=%d ldx=%ld n_eps=%d capacity=%lld",
                 (long long)N, D, ldx, n_eps, (long long)capacity);
-    DIC_REQUIRE(D <= DB_D && D % 4 == 0 && ldx % 4 == 0, DIC_ERR_UNSUPPORTED, "dbscan_counts: D=%d (row stride %ld): at most %d, multiples of 4", D, ldx, DB_D);
+    DIC_REQUIRE(D <= PT_D && D % 4 == 0 && ldx % 4 == 0, DIC_ERR_UNSUPPORTED, "dbscan_counts: D=%d (row stride %ld): at most %d, multiples of 4", D, ldx, PT_D);
     DIC_REQUIRE(N < (1LL << 30) && n_eps <= DB_MAX_EPS, DIC_ERR_UNSUPPORTED, "dbscan_counts: N=%lld n_eps=%d (at most %d)", (long long)N, n_eps, DB_MAX_EPS);
     DIC_REQUIRE(X && centre && thresholds && counts && n_band && workspace && (band || capacity == 0), DIC_ERR_INVALID_ARG, "dbscan_counts: NULL pointer");
     DIC_REQUIRE(((uintptr_t)X & 15) == 0 && ((uintptr_t)centre & 15) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)band & 15) == 0,
                 DIC_ERR_UNSUPPORTED, "dbscan_counts: operands must be 16-B aligned");
     DIC_REQUIRE(workspace_bytes >= dic_dbscan_workspace(N, D), DIC_ERR_WORKSPACE, "dbscan_counts: workspace %zu < %zu", workspace_bytes,
                 dic_dbscan_workspace(N, D));
-    for (int e = 0; e < n_eps; ++e)
+    for (int e = 0; e < n_eps; ++e) {
         DIC_REQUIRE(thresholds[e] >= 0.f, DIC_ERR_INVALID_ARG, "dbscan_counts: threshold %d = %g", e, (double)thresholds[e]);
+        DIC_REQUIRE(thresholds[e] < DB_MAX_THRESHOLD, DIC_ERR_UNSUPPORTED, "dbscan_counts: threshold %d = %g: below 2^100 (eps < 2^50)", e, (double)thresholds[e]);
+    }
     int rc = db_reserve_lds();
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     unsigned char* ws = (unsigned char*)workspace;
-    const DbLayout o = db_layout(N);
-    const long plane = (long)((N + DB_T) * DB_LD);
-    __bf16* pa = (__bf16*)(ws + o.pa);
-    __bf16* pb = (__bf16*)(ws + o.pb);
-    float* nrm = (float*)(ws + o.nrm);
-    unsigned long long* cnt_dev = (unsigned long long*)(ws + o.count);
-    // padding rows behind the last point are read by the last tiles (and masked): zero, and norm 0
-    hipError_t e = hipMemsetAsync(pa + (size_t)N * DB_LD, 0, (size_t)DB_T * DB_LD * sizeof(__bf16), st);
-    if (e == hipSuccess) e = hipMemsetAsync(pa + plane + (size_t)N * DB_LD, 0, (size_t)DB_T * DB_LD * sizeof(__bf16), st);
-    if (e == hipSuccess) e = hipMemsetAsync(pb + (size_t)N * DB_LD, 0, (size_t)DB_T * DB_LD * sizeof(__bf16), st);
-    if (e == hipSuccess) e = hipMemsetAsync(pb + plane + (size_t)N * DB_LD, 0, (size_t)DB_T * DB_LD * sizeof(__bf16), st);
-    if (e == hipSuccess) e = hipMemsetAsync(nrm + N, 0, (size_t)DB_T * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(cnt_dev, 0, sizeof(unsigned long long), st);
+    unsigned long long* cnt_dev = (unsigned long long*)(ws + pt_layout(N).count);
+    hipError_t e = hipMemsetAsync(cnt_dev, 0, sizeof(unsigned long long), st);
     if (e == hipSuccess) e = hipMemsetAsync(counts, 0, (size_t)n_eps * N * sizeof(int32_t), st);
     DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "dbscan_counts: memset: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(db_prep_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, X, ldx, centre, (int)N, D, pa, pb, plane, nrm);
-    const int nblk = (int)((N + DB_T - 1) / DB_T);
-    hipLaunchKernelGGL(db_block_max_kernel, dim3(nblk), dim3(256), 0, st, (const float*)nrm, (int)N, (float*)(ws + o.bmax));
+    rc = pt_prepare_planes(X, ldx, centre, N, D, PT_PAD_NORM, ws, st, "dbscan_counts");
+    if (rc) return rc;
     DbTileArgs t{};
-    db_fill_tile_args(t, ws, N);
+    pt_fill_pair_args(t.p, ws, N);
     const int ne = n_eps <= 1 ? 1 : n_eps <= 4 ? 4 : n_eps <= 10 ? 10 : 16;
     for (int q = 0; q < DB_MAX_EPS; ++q) {
         if (q < n_eps) {
@@ -552,12 +328,12 @@ int dic_dbscan_counts(const float* X, long ldx, const float* centre, int64_t N, 
     t.band = (di32x4*)band;
     t.cap = capacity;
     t.band_count = cnt_dev;
-    const dim3 grid(db_grid(t.ntiles)), blk(512);
+    const dim3 grid(pt_grid(t.p.ntiles)), blk(512);
     switch (ne) {
-        case 1: hipLaunchKernelGGL((db_tile_kernel<0, 1>), grid, blk, DB_LDS, st, t); break;
-        case 4: hipLaunchKernelGGL((db_tile_kernel<0, 4>), grid, blk, DB_LDS, st, t); break;
-        case 10: hipLaunchKernelGGL((db_tile_kernel<0, 10>), grid, blk, DB_LDS, st, t); break;
-        default: hipLaunchKernelGGL((db_tile_kernel<0, 16>), grid, blk, DB_LDS, st, t); break;
+        case 1: hipLaunchKernelGGL(db_count_kernel<1>, grid, blk, PT_LDS, st, t); break;
+        case 4: hipLaunchKernelGGL(db_count_kernel<4>, grid, blk, PT_LDS, st, t); break;
+        case 10: hipLaunchKernelGGL(db_count_kernel<10>, grid, blk, PT_LDS, st, t); break;
+        default: hipLaunchKernelGGL(db_count_kernel<16>, grid, blk, PT_LDS, st, t); break;
     }
     rc = check_launch("dbscan_counts");
     if (rc) return rc;
@@ -578,20 +354,21 @@ int dic_dbscan_components_pass(int64_t N, int D, float threshold, int eps_index,
                                int32_t* labels, int32_t* border, int32_t* changed, void* workspace, size_t workspace_bytes, dic_stream_t stream) {
     DIC_REQUIRE(N > 0 && D > 0 && eps_index >= 0 && n_band >= 0 && min_samples >= 1, DIC_ERR_INVALID_ARG,
                 "dbscan_components_pass: N=%lld D=%d eps_index=%d n_band=%lld min_samples=%d", (long long)N, D, eps_index, (long long)n_band, min_samples);
-    DIC_REQUIRE(D <= DB_D && N < (1LL << 30) && eps_index < DB_MAX_EPS, DIC_ERR_UNSUPPORTED, "dbscan_components_pass: N=%lld D=%d eps_index=%d", (long long)N,
+    DIC_REQUIRE(D <= PT_D && N < (1LL << 30) && eps_index < DB_MAX_EPS, DIC_ERR_UNSUPPORTED, "dbscan_components_pass: N=%lld D=%d eps_index=%d", (long long)N,
                 D, eps_index);
     DIC_REQUIRE(counts_e && labels && border && changed && workspace && (band || n_band == 0), DIC_ERR_INVALID_ARG, "dbscan_components_pass: NULL pointer");
     DIC_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)band & 15) == 0, DIC_ERR_UNSUPPORTED, "dbscan_components_pass: operands must be 16-B aligned");
     DIC_REQUIRE(workspace_bytes >= dic_dbscan_workspace(N, D), DIC_ERR_WORKSPACE, "dbscan_components_pass: workspace %zu < %zu", workspace_bytes,
                 dic_dbscan_workspace(N, D));
     DIC_REQUIRE(threshold >= 0.f, DIC_ERR_INVALID_ARG, "dbscan_components_pass: threshold %g", (double)threshold);
+    DIC_REQUIRE(threshold < DB_MAX_THRESHOLD, DIC_ERR_UNSUPPORTED, "dbscan_components_pass: threshold %g: below 2^100 (eps < 2^50)", (double)threshold);
     int rc = db_reserve_lds();
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemsetAsync(border, 0x7f, (size_t)N * sizeof(int32_t), st);
     DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "dbscan_components_pass: memset: %s", hipGetErrorString(e));
     DbTileArgs t{};
-    db_fill_tile_args(t, (unsigned char*)workspace, N);
+    pt_fill_pair_args(t.p, (unsigned char*)workspace, N);
     for (int q = 0; q < DB_MAX_EPS; ++q) t.thr.t[q] = t.thr.tl[q] = t.thr.th[q] = -1.f;
     t.thr.t[0] = threshold;
     db_margins(threshold, t.thr.tl[0], t.thr.th[0]);
@@ -601,7 +378,7 @@ int dic_dbscan_components_pass(int64_t N, int D, float threshold, int eps_index,
     t.L = labels;
     t.border = border;
     t.changed = changed;
-    hipLaunchKernelGGL((db_tile_kernel<1, 1>), dim3(db_grid(t.ntiles)), dim3(512), DB_LDS, st, t);
+    hipLaunchKernelGGL(db_label_kernel, dim3(pt_grid(t.p.ntiles)), dim3(512), PT_LDS, st, t);
     if (n_band > 0)
         hipLaunchKernelGGL(db_band_link_kernel, dim3((unsigned)((n_band + 255) / 256)), dim3(256), 0, st, (const di32x4*)band, (long long)n_band, eps_index,
                            counts_e, min_samples, labels, border, changed);

@@ -1,10 +1,10 @@
 // The k-th neighbour distance of every point (p2_clustering_optK.py:110-112: NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X)[0][:, -1]; also OPTICS' core
 // distance): kth[i] = the k-th smallest of { |x_i - x_j| : j = 0..N-1 }, the self pair included (k = 1 gives 0), as the f64 square root of the f64
 // difference-form squared distance of the f32 coordinates.  Nothing N x N is stored: the pairs are recomputed tile by tile on the matrix cores
-// (dic_pairtile.h, the machine of dic_dbscan.hip), selection instead of thresholding.
+// (dic_pairtile.h, the machine dic_dbscan.hip thresholds on), selection instead of thresholding.
 //
 // THE APPROXIMATE d^2 ONLY NARROWS THE SEARCH.  a_ij is the tile loop's split-bf16 value; it is a fixed function of (i, j) (a tile's accumulation does not
-// depend on which workgroup walks it or in which launch), and |a_ij - d^2_ij| < B0 = 2^-12 (n_i + nmax_J) (dic_dbscan.hip).  Per row this file uses the wider
+// depend on which workgroup walks it or in which launch), and |a_ij - d^2_ij| < B0 = 2^-12 (n_i + nmax_J) (dic_pairtile.h).  Per row this file uses the wider
 //   B_i = 2^-12 (n_i + nmax),   nmax the largest norm of all points,   so |a_ij - d^2_ij| < B_i for every j.
 // (1) COUNTING PASSES select on the a values, exactly: every row keeps a bracket (lo_i, hi_i] with  #{j : a_ij <= lo_i} < k <= #{j : a_ij <= hi_i}.  It starts
 //     at lo = -2 B_i - tiny (every a_ij > -B_i: count 0) and hi = (sqrt n_i + sqrt nmax)^2 + 2 B_i (every a_ij below it: count N >= k).  A pass counts, for
@@ -34,7 +34,6 @@ namespace dic {
 constexpr int KN_T = 16;                               // thresholds per row and refining pass
 constexpr int KN_REFINE = 3;                           // refining passes
 constexpr int KN_ENTRY = 12;                           // bytes of candidate storage per list entry: int32 index + f64 d^2
-constexpr float KN_PAD_NORM = 0x1p120f;                // the norm the padding points present as j: their a_ij = n_i + 2^120 lies above every threshold
 constexpr long long KN_DEFAULT_BUDGET = 384LL << 20;   // bytes (list sizes at 75 000 x 256)
 
 struct KnLayout { size_t thr, cnt, lo, hi, bnd, off, cursor, bounds, plan, idx, d2, total; long long entries; };
@@ -246,7 +245,7 @@ struct KnCount {
             for (int nb = 0; nb < 4; ++nb)
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
-                    const float d2 = acc[nb][mb][k];          // (a padding point j is beyond every threshold: KN_PAD_NORM; a padding row i is never flushed)
+                    const float d2 = acc[nb][mb][k];          // (a padding point j is beyond every threshold: PT_PAD_NORM; a padding row i is never flushed)
 #pragma unroll
                     for (int q = 0; q < T; ++q) c[q] += (int)(d2 <= t[q]);
                 }
@@ -274,7 +273,7 @@ struct KnGather {
 #pragma unroll
                 for (int k = 0; k < 16; ++k) {
                     const float d2 = acc[nb][mb][k];
-                    const bool in = iv && d2 > wlo && d2 <= whi;          // (a padding point j is beyond every window: KN_PAD_NORM)
+                    const bool in = iv && d2 > wlo && d2 <= whi;          // (a padding point j is beyond every window: PT_PAD_NORM)
                     bits[nb >> 1] |= in ? (1u << (16 * (nb & 1) + k)) : 0u;
                 }
             const int nbits = __builtin_popcount(bits[0]) + __builtin_popcount(bits[1]);
@@ -365,16 +364,8 @@ __global__ __launch_bounds__(256) void kn_exact_kernel(const float* X, long ldx,
 }
 
 static int kn_reserve_lds() {
-    static bool attr_set = false;
-    if (!attr_set) {
-        const void* fns[] = {(const void*)kn_count_kernel<KN_T>, (const void*)kn_count_kernel<2>, (const void*)kn_gather_kernel};
-        for (const void* f : fns) {
-            hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS);
-            DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn: cannot reserve %d B of LDS: %s", PT_LDS, hipGetErrorString(e));
-        }
-        attr_set = true;
-    }
-    return DIC_OK;
+    static bool done = false;
+    return pt_reserve_lds(done, {(const void*)kn_count_kernel<KN_T>, (const void*)kn_count_kernel<2>, (const void*)kn_gather_kernel}, "knn");
 }
 
 }  // namespace dic
@@ -404,7 +395,7 @@ int dic_knn_kth_distance(const float* X, long ldx, const float* centre, int64_t 
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     unsigned char* ws = (unsigned char*)workspace;
-    rc = pt_prepare_planes(X, ldx, centre, N, D, KN_PAD_NORM, ws, st, "knn_kth_distance");
+    rc = pt_prepare_planes(X, ldx, centre, N, D, PT_PAD_NORM, ws, st, "knn_kth_distance");
     if (rc) return rc;
     KnTileArgs t{};
     pt_fill_pair_args(t.p, ws, N);

@@ -1,8 +1,24 @@
-// The pair-tile machine of dic_dbscan.hip as a header: the split-bf16 planes of the centred points, their layout in a workspace, and the persistent 256 x 256
-// tile loop, whose result -- the approximate d^2 of 2 x 64 (i, j) pairs per lane, in registers -- goes to an epilogue the caller supplies.  The planes, the
-// products and hence the error bound of that d^2 are those derived at the top of dic_dbscan.hip (B0 = 2^-12 (n_i + nmax_J)); nothing here decides anything.
-// dic_knn.hip is built on it.  dic_dbscan.hip keeps its own copy of the loop: moving its kernels onto this header changes their register allocation.
+// The pair-tile machine DBSCAN (dic_dbscan.hip) and the k-th neighbour distances (dic_knn.hip) are built on: the split-bf16 planes of the centred points, their
+// layout in a workspace, and the persistent 256 x 256 tile loop, whose result -- the approximate d^2 of 2 x 64 (i, j) pairs per lane, in registers -- goes to
+// an epilogue the caller supplies.  Nothing here decides anything.
+//
+// PAIR PASSES.  The machine of dic_intra.hip's intra_x3_kernel<ROWS>: one persistent 8-wave workgroup per CU walks a contiguous range of the (I, J) list of
+// 256 x 256 point-pair tiles (ALL ordered block pairs, row-major), both operands' 32-column slabs streamed through LDS-DMA rings; d^2 = n_i + n_j - 2 v_i . v_j
+// is one inner product of 288-column augmented rows, v = x - centre (f32), every coordinate as bf16 hi + lo with the products hi.hi + lo.hi + hi.lo, the f32
+// norms n = sum v^2 as three exact bf16 pieces.  Lane = point i, registers = points j: a lane's per-i results stay in registers while its workgroup's range
+// stays on one row block I and are flushed by the epilogue (integer atomics: exact, order-free) when I changes.
+//
+// ERROR BOUND of the approximate d^2 (call it a_ij) against the exact d^2_ij of the f32 points, u = 2^-24:
+//   (1) v = fl(x - centre): each coordinate of v_i - v_j is off by <= u (|v_ik| + |v_jk|), so |d_v^2 - d^2| <= 2u (|v_i| + |v_j|)^2 (1 + u) <= 4.1u (n_i + n_j).
+//   (2) the split: h = bf16(v), |v - h| <= 2^-8 |v|; l = bf16(v - h) (v - h exact in f32), |v - h - l| <= 2^-16 |v|.  The dropped part of a product a.b is
+//       l_a l_b + r_a b + (h_a + l_a) r_b, <= 3.1 * 2^-16 |a| |b|; b = -2 v_j splits exactly as -2 (h, l), so -2 v_i . v_j is off by
+//       <= 6.2 * 2^-16 sum_k |v_ik| |v_jk| <= 3.1 * 2^-16 (n_i + n_j).
+//   (3) f32 accumulation: 288 / 16 * 3 = 54 chained MFMAs of 16 exact products each, at most 54 * 16 = 864 roundings in sequence, each of
+//       sum |terms| <= (n_i + n_j) + 2 * (1 + 2^-7) sum |v_ik v_jk| <= 2.02 (n_i + n_j):  <= 864 u * 2.02 (n_i + n_j) <= 2^-13.2 (n_i + n_j).
+//   (4) the norms' own f32 rounding (4 fmas + 6 shuffle adds): <= 10u (n_i + n_j).
+//   Together |a_ij - d^2_ij| < (0.11 + 0.19 + 0.43 + 0.01) 2^-12 (n_i + n_j) < B0 = 2^-12 (n_i + nmax_J), nmax_J the largest n of j's 256-row block.
 #pragma once
+#include <initializer_list>
 #include "dic_common.h"
 
 namespace dic {
@@ -24,6 +40,8 @@ constexpr int PT_SLABS = PT_LD / PT_K;                 // 9
 constexpr int PT_NI = 3, PT_NJ = 2;                    // ring depths of the two operands
 constexpr int PT_LDS = (PT_NI + PT_NJ) * PT_SLOT;      // 163 840 B
 static_assert(PT_LDS <= 160 * 1024, "pair tiles: LDS budget");
+// The norm the padding points present as j where an epilogue does not mask by index: their a_ij = 2^120 lies above every threshold a caller admits.
+constexpr float PT_PAD_NORM = 0x1p120f;
 
 // Workspace of the planes: pa / pb (hi | lo planes of the two operands, N + 256 rows each), the f32 norms (N + 256), the largest norm of every 256-row block,
 // and one 256-B scratch word block for the caller.
@@ -64,6 +82,17 @@ inline void pt_fill_pair_args(PtPairArgs& t, unsigned char* ws, int64_t N) {
 }
 
 inline unsigned pt_grid(long long ntiles) { return (unsigned)(ntiles < 1 ? 1 : ntiles < (long long)kNumCU ? ntiles : (long long)kNumCU); }
+
+// The tile kernels `fns` of a file get the loop's dynamic LDS, once per process (`done` is the caller's).
+inline int pt_reserve_lds(bool& done, std::initializer_list<const void*> fns, const char* who) {
+    if (done) return DIC_OK;
+    for (const void* f : fns) {
+        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, PT_LDS);
+        DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "%s: cannot reserve %d B of LDS: %s", who, PT_LDS, hipGetErrorString(e));
+    }
+    done = true;
+    return DIC_OK;
+}
 
 // Augmented rows relative to one centre, and the f32 norms.  One wave per point: lane l holds coordinates 4 l .. 4 l + 3.
 static __global__ __launch_bounds__(256) void pt_prep_kernel(const float* X, long ldx, const float* mu, int n, int d, __bf16* pa, __bf16* pb, long plane, float* nrm_out) {

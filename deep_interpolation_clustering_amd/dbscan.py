@@ -16,6 +16,7 @@ from . import _native as N
 
 MAX_EPS_PER_PASS = 16           # dic_dbscan_counts: thresholds per counting pass
 MAX_DIM = 256
+MAX_SQ_THRESHOLD = 2.0 ** 100   # dic_dbscan_counts: squared-distance thresholds stay below it (the padding points sit at 2^120), i.e. eps < 2^50
 
 
 def sq_threshold(eps):
@@ -111,6 +112,10 @@ def dbscan_sweep(X, eps_values, min_samples, band_capacity=None, stats=None):
     if min_samples < 1:
         raise ValueError('min_samples must be >= 1, got %d' % min_samples)
     eps_values = list(eps_values)
+    thresholds = [sq_threshold(e) for e in eps_values]
+    for e, t in zip(eps_values, thresholds):
+        if not t < MAX_SQ_THRESHOLD:
+            raise ValueError('dbscan: eps must be below 2^50 (about 1.1e15), got %r' % (e,))
     x = _device_points(X)
     if x.shape[1] > MAX_DIM:
         raise NotImplementedError('dbscan: at most %d features (got %d)' % (MAX_DIM, x.shape[1]))
@@ -120,8 +125,8 @@ def dbscan_sweep(X, eps_values, min_samples, band_capacity=None, stats=None):
         stats.setdefault('components_passes', [])
         stats.setdefault('counts_reruns', 0)
     for g in range(0, len(eps_values), MAX_EPS_PER_PASS):
-        group = eps_values[g:g + MAX_EPS_PER_PASS]
-        cp = _Counts(x, [sq_threshold(e) for e in group], band_capacity)
+        group = thresholds[g:g + MAX_EPS_PER_PASS]
+        cp = _Counts(x, group, band_capacity)
         for e in range(len(group)):
             labels, core, passes = cp.components(e, min_samples)
             out.append((labels, np.flatnonzero(core).astype(np.int64)))

@@ -595,7 +595,7 @@ int dic_gemm_tn_planes(const void* A_hi, long a_plane, long lda, const float* X,
  * pairwise_distances(X) and fit DBSCAN(eps, min_samples, metric='precomputed') on it; these recompute the distances tile by tile on the matrix cores.
  * X (N, D) f32 at row stride ldx, D <= 256, D % 4 == 0 (zero-pad narrower points), N < 2^30, 16-B aligned.  Neighbour rule (sklearn's): (i, j) are
  * neighbours for eps e iff f32(||x_i - x_j||^2) <= thresholds[e], thresholds[e] the largest f32 s with sqrt_f32(s) <= eps under NumPy's promotion of the
- * caller's eps (dbscan.py); the self pair counts.  One workspace (dic_dbscan_workspace(N, D) bytes) serves the counting pass and, unchanged, every
+ * caller's eps (dbscan.py); the self pair counts.  Thresholds lie in [0, 2^100) (eps < 2^50); one beyond returns DIC_ERR_UNSUPPORTED.  One workspace (dic_dbscan_workspace(N, D) bytes) serves the counting pass and, unchanged, every
  * components pass after it (it holds the split planes of the points).
  *   dic_dbscan_counts: counts (n_eps, N) int32 OVERWRITTEN = |N_eps(i)| for every eps (n_eps <= 16) in ONE pair pass; centre (1, D) f32 = the mean of the
  *       points.  A pair whose approximate d^2 lies within the derived error bound of some threshold is a BAND pair: appended to band (capacity, 4) int32 as

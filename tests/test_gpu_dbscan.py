@@ -1,5 +1,6 @@
 """DBSCAN on the GPU (dbscan.py, csrc/dic_dbscan.hip) against sklearn's fit on the precomputed distance matrix -- the path upstream takes
 (p2_clustering_optK.py:82-85,90-168, p4_clustering_final.py:181-236).  Labels and core indices must be identical."""
+import functools
 import os
 
 import numpy as np
@@ -8,7 +9,7 @@ import torch
 
 from deep_interpolation_clustering_amd import _native as N
 from deep_interpolation_clustering_amd import cluster_stats
-from deep_interpolation_clustering_amd.dbscan import DBSCAN, dbscan_sweep, sq_threshold
+from deep_interpolation_clustering_amd.dbscan import DBSCAN, _Counts, _device_points, dbscan_sweep, sq_threshold
 from deep_interpolation_clustering_amd.info import COHORTS
 
 pytestmark = pytest.mark.gpu
@@ -185,6 +186,68 @@ def test_band_overflow_reruns_exactly():
     thr = (N.C.c_float * 1)(sq_threshold(eps))
     rc = L.dic_dbscan_counts(N.ptr(x), d, N.ptr(centre), n, d, thr, 1, N.ptr(counts), N.ptr(band), 1, N.C.byref(nb), N.ptr(ws), ws.numel(), N.stream_of(x))
     assert rc == -3 and nb.value > 1
+
+
+@functools.lru_cache(maxsize=None)
+def centred_points(n):
+    """(X (n, 8) f32, exact f64 squared distances (n, n)): 40 points at the origin, the others on the 2^-12 grid at radius 0.2 .. 0.99 as +- pairs and one
+    triple a, b, -(a + b), shuffled, a point of the origin last.  Every coordinate sum is exactly 0, so the centre the kernel gets is the origin itself and the
+    zero vector -- which is also what a padding point holds -- is a real point; on the grid the f64 squared distances are exact."""
+    rng = np.random.default_rng(2 + n)          # (a seed at which the audit below holds for every case)
+    m = (n - 40 - 3) // 2
+    assert 40 + 3 + 2 * m == n
+    v = rng.normal(0, 1, (m + 2, 8))
+    v = np.round(v / np.linalg.norm(v, axis=1, keepdims=True) * rng.uniform(0.2, 0.99, (m + 2, 1)) * 0.5 * 4096) / 4096
+    a, b, half = v[0], v[1], v[2:]
+    rest = rng.permutation(np.concatenate([2 * half, -2 * half, [a, b, -(a + b)], np.zeros((39, 8))]))
+    X = np.concatenate([rest, np.zeros((1, 8))])
+    assert X.shape == (n, 8) and not X.sum(0).any() and np.linalg.norm(X, axis=1).max() <= 1.0 and (X.astype(np.float32) == X).all()
+    d2 = ((X[:, None, :] - X[None, :, :]) ** 2).sum(-1)
+    d2.setflags(write=False)
+    return X.astype(np.float32), d2
+
+
+def brute_dbscan(d2, eps, min_samples):
+    """sklearn's _dbscan_inner on the neighbour rule f32(d^2) <= sq_threshold(eps): (neighbour counts, labels, core indices)."""
+    nb = d2.astype(np.float32) <= np.float32(sq_threshold(eps))
+    counts = nb.sum(1)
+    core = counts >= min_samples
+    lab = np.full(len(d2), -1, np.int64)
+    cid = 0
+    for i in np.flatnonzero(core):
+        if lab[i] >= 0:
+            continue
+        lab[i] = cid
+        stack = [i]
+        while stack:
+            for q in np.flatnonzero(nb[stack.pop()] & (lab < 0)):
+                lab[q] = cid
+                if core[q]:
+                    stack.append(q)
+        cid += 1
+    return counts, lab, np.flatnonzero(core).astype(np.int64)
+
+
+def padding_eps(n_eps):
+    """n_eps values from 1e-3, which isolates every point that has no duplicate, to 1e6, which makes every pair a neighbour (alone: the latter)."""
+    return [1e6] if n_eps == 1 else [1e-3] + [float(e) for e in np.linspace(0.25, 1.0, n_eps - 2)] + [1e6]
+
+
+# 257: two row blocks, 255 padding points in the last one; 513: the last point alone in its row block.  D = 8: zero-padded columns.
+@pytest.mark.parametrize('n,n_eps', [(257, 1), (257, 4), (257, 10), (257, 16), (513, 10)])
+def test_padding_points_are_never_neighbours(n, n_eps):
+    X, d2 = centred_points(n)
+    eps = padding_eps(n_eps)
+    audit(X, eps)
+    ref = [brute_dbscan(d2, e, 5) for e in eps]
+    assert (ref[-1][0] == n).all() and (n_eps == 1 or (ref[0][0][np.any(X != 0, axis=1)] == 1).all())
+    fits = dbscan_sweep(X, eps, 5)
+    for (_, ref_lab, ref_core), (lab, core) in zip(ref, fits):
+        np.testing.assert_array_equal(core, ref_core)
+        np.testing.assert_array_equal(lab, ref_lab)
+    counts = _Counts(_device_points(X), [sq_threshold(e) for e in eps]).counts.cpu().numpy()
+    assert (counts[-1] == n).all()
+    np.testing.assert_array_equal(counts, np.stack([c for c, _, _ in ref]))
 
 
 def test_sweep_equals_fits_and_repeats():
