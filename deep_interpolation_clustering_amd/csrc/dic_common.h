@@ -29,6 +29,17 @@ int check_launch(const char* what);
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// Compute units of the current device, asked once: a persistent grid sized by it (one workgroup per CU) runs one round on a smaller part or
+// partition too, where kNumCU workgroups would quietly run two.
+inline int device_cus() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v < 1) v = kNumCU;
+        return v;
+    }();
+    return n;
+}
+
 // dic_kmeans_mfma.hip: E-step + partial M-step of a Lloyd iteration on the matrix cores, for 8 < K <= 32
 int kmeans_mfma_blocks(int N, int K, int n_runs);
 bool kmeans_use_mfma(int K, int n_runs);
@@ -72,6 +83,16 @@ __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_ex
 // term is 1), so its missing denormal handling never shows; e^-inf = 0, NaN propagates.
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * kLog2e); }
 __device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.6931471805599453f; }
+
+// relu of packed bf16 pairs as ONE integer instruction per register: a negative bf16 is a negative int16, so max(x, 0) on the 16-bit
+// halves (v_pk_max_i16) zeroes exactly the negative halves (and -0.0); `floor` = 0 applies it, 0x8000 per half (INT16_MIN) is the identity
+typedef short ps16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ unsigned pk_relu(unsigned x, unsigned floor) {
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(ps16x2, x), __builtin_bit_cast(ps16x2, floor)));
+}
+__device__ __forceinline__ uint4 pk_relu4(uint4 v, unsigned floor) {
+    return make_uint4(pk_relu(v.x, floor), pk_relu(v.y, floor), pk_relu(v.z, floor), pk_relu(v.w, floor));
+}
 
 // log(1 + e^k): the positive bandwidth upstream derives from its raw `kernel` parameter
 // (interpolation_layer.py:51, rbf.py:78).

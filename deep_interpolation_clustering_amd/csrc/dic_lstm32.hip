@@ -291,6 +291,7 @@ struct FwdXArgs {
     __bf16* gates; __bf16* cs;      // lane-native (R,Bp,2,4,H) / (R,Bp,2,H), Bp = B rounded up to 64; or NULL
     int R, B, bm, boundary, relu_x;
     __bf16* out_r;                  // optional (R,B,2H): relu(out), for a consumer that rectifies the output (as dic_lstm_fwd's out_r)
+    int nbt;                        // 32-row tiles per direction, of the batch padded to 64 rows (the grid is smaller: see the kernel)
 };
 constexpr int XI = 256;                 // decoder input width (2H)
 constexpr int XIP = XI + 8;             // LDS row pitch of the x tile (528 B: conflict-free 16-B reads)
@@ -317,8 +318,16 @@ __device__ unsigned long long dic_fwdx_stamps[8][32][8];
         if (blockIdx.x == 7 && blockIdx.y == 0 && (threadIdx.x & 63) == 0 && (step) < 32)                              \
             dic_fwdx_stamps[threadIdx.x >> 6][step][slot] = __builtin_readcyclecounter();                              \
     } while (0)
+// outside the step loop: slot 6 of steps 0 / 1 / 2 = entry / the first step of the workgroup's first tile begins / just before exit; slot 7: the same moments
+// on the constant 100 MHz clock, which turns the cycles into time
+#define FX_STAMP_WG(which)                                                                                             \
+    do {                                                                                                              \
+        FX_STAMP(which, 6);                                                                                           \
+        if (blockIdx.x == 7 && blockIdx.y == 0 && (threadIdx.x & 63) == 0) dic_fwdx_stamps[threadIdx.x >> 6][which][7] = wall_clock64(); \
+    } while (0)
 #else
 #define FX_STAMP(step, slot) do {} while (0)
+#define FX_STAMP_WG(which) do {} while (0)
 #endif
 
 __global__ __launch_bounds__(512, 1) void lstm_fwdx8_kernel(FwdXArgs a) {
@@ -332,12 +341,14 @@ __global__ __launch_bounds__(512, 1) void lstm_fwdx8_kernel(FwdXArgs a) {
     T* wl = reinterpret_cast<T*>(bsm + S4);                              // [4H][X8LP]
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, hh = lane >> 5;
     const int w8 = __builtin_amdgcn_readfirstlane(tid >> 6), w4 = w8 >> 1, qh = w8 & 1;
-    const int dir = blockIdx.y, b0 = blockIdx.x * SROWS, B = a.B, R = a.R;
-    const int nbt = gridDim.x, bt = blockIdx.x;
-    const int b = b0 + r;
-    const bool ok = b < B;
-    const int bc = min(b, B - 1);
+    const int dir = blockIdx.y, B = a.B, R = a.R;
+    const int nbt = a.nbt, W = gridDim.x;
+    FX_STAMP_WG(0);
 
+    // Persistent: the grid is (W, 2), one workgroup per CU, and workgroup (w, dir) walks the tiles w, w + W, w + 2 W, ... of its direction (a trip count
+    // known at entry: no counters, no flags, no waiting on another workgroup).  Everything up to the tile loop is the same for every tile of a direction
+    // and is done once per CU: the weight fragments below (160 KB into registers), the LDS images of W_ih's last columns and of the bias (74 KB).  One
+    // workgroup per tile paid for that, for its own dispatch and for its predecessor's drain 2048 times at B = 32 768.
     // A rows of block blk: m = lane & 31 -> gate 2 blk + (m >> 4), unit 16 w8 + (m & 15)
     sbf16x8 wh[2][SH / 16], wx[2][X8RK / 16];
     const int arow[2] = {(0 + (r >> 4)) * SH + 16 * w8 + (r & 15), (2 + (r >> 4)) * SH + 16 * w8 + (r & 15)};
@@ -355,24 +366,6 @@ __global__ __launch_bounds__(512, 1) void lstm_fwdx8_kernel(FwdXArgs a) {
         *reinterpret_cast<sbf16x8*>(wl + row * X8LP + pc * 8) = *reinterpret_cast<const sbf16x8*>(a.wih + ((size_t)dir * S4 + row) * XI + X8RK + pc * 8);
     }
 
-    float c[8];                      // element e = 4 qq + j: unit 16 w8 + 8 qq + 4 hh + j
-#pragma unroll
-    for (int qq = 0; qq < 2; ++qq) {
-        const int u = 16 * w8 + 8 * qq + 4 * hh;
-        sf32x4 hv = {0.f, 0.f, 0.f, 0.f}, cv = {0.f, 0.f, 0.f, 0.f};
-        if (ok) {
-            if (a.h0) hv = *reinterpret_cast<const sf32x4*>(a.h0 + sstate_off(a.bm, dir, b, B) + u);
-            if (a.c0) cv = *reinterpret_cast<const sf32x4*>(a.c0 + sstate_off(a.bm, dir, b, B) + u);
-        }
-        V4 hb;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { hb[j] = (T)hv[j]; c[4 * qq + j] = cv[j]; }
-        *reinterpret_cast<V4*>(hbuf0 + r * HP + u) = hb;
-        if (a.boundary && ok) {
-            T* slot = dir ? a.out + (size_t)R * B * 2 * SH : a.out - (size_t)B * 2 * SH;
-            *reinterpret_cast<V4*>(slot + (size_t)b * 2 * SH + dir * SH + u) = hb;
-        }
-    }
     // x tile of a step: 32 rows x 32 pieces of 16 B, two per thread; rectified on the way into LDS.  (Round 5 tried the tile by LDS-DMA into three swizzled
     // buffers behind a counted vmcnt wait -- the compiler's wait for these register loads is `vmcnt(0)`, a drain of the step's stores -- and two steps of
     // distance through two register sets: interleaved two-library A/Bs, scripts/two_lib_ab.py: DMA 951-969 us against 936-941 with 8-B stores, ~900 against
@@ -380,31 +373,31 @@ __global__ __launch_bounds__(512, 1) void lstm_fwdx8_kernel(FwdXArgs a) {
     typedef unsigned xu32x4 __attribute__((ext_vector_type(4)));
     const int xrow = tid >> 4, xpc = tid & 15;               // pieces xpc, xpc + 16
     xu32x4 xn[2];
-    auto load_x = [&](int step) {
-        const int t = dir ? R - 1 - step : step;
-        const T* src = a.x + ((size_t)t * B + min(b0 + xrow, B - 1)) * XI;
+    // The x tiles of all the steps of all this workgroup's tiles form ONE sequence, staged two ahead of the step that reads them: the last two steps of a
+    // tile land / request the first two x tiles of the next one, so a tile boundary exposes no round trip for x.  (xbt, xs) = (tile, step) of the next
+    // request; xbt >= nbt: the sequence is exhausted.
+    int xbt = blockIdx.x, xs = 0;
+    auto load_x = [&]() {
+        const int t = dir ? R - 1 - xs : xs;
+        const T* src = a.x + ((size_t)t * B + min(xbt * SROWS + xrow, B - 1)) * XI;
 #pragma unroll
         for (int k = 0; k < 2; ++k) xn[k] = *reinterpret_cast<const xu32x4*>(src + (xpc + 16 * k) * 8);
+        if (++xs == R) { xs = 0; xbt += W; }
     };
+    const unsigned xfloor = a.relu_x ? 0u : 0x80008000u;    // pk_relu (dic_common.h): one v_pk_max_i16 per dword
     auto land_x = [&](int buf) {
         T* dst = xbuf + buf * SROWS * XIP + xrow * XIP;
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             xu32x4 v = xn[k];
-            if (a.relu_x) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const unsigned neg = ((v[e] >> 15) & 0x00010001u) * 0xFFFFu;
-                    v[e] &= ~neg;
-                }
-            }
+            for (int e = 0; e < 4; ++e) v[e] = pk_relu(v[e], xfloor);
             *reinterpret_cast<xu32x4*>(dst + (xpc + 16 * k) * 8) = v;
         }
     };
-    load_x(0);
+    load_x();
     land_x(0);
-    if (R > 1) load_x(1);
-    __syncthreads();
+    if (xbt < nbt) load_x();
     // pieces A and B (`delta` elements apart) of the lane-native saved state, one 16-B store per lane (see the store comment in the step loop)
     const bool odd = lane & 1;
     const int pslot = (hh * 32 + (r & ~1)) * 4;                 // the even lane's slot of the pair, in elements
@@ -426,132 +419,164 @@ __global__ __launch_bounds__(512, 1) void lstm_fwdx8_kernel(FwdXArgs a) {
     // (Running the two waves of a SIMD half a step apart -- one wave's projection MFMAs under the other's gate arithmetic, x tiles staged two steps ahead --
     //  was tried: no change, 0.76 ms without the saved-state stores either way.  A step costs the sum of its parts: 96 MFMAs and ~590 vector instructions per
     //  SIMD, 160 of them quarter-rate exp / rcp: 3.9 us, against 3.0 us of HBM time for its 64 KB.)
-    for (int step = 0; step < R; ++step) {
-        const int t = dir ? R - 1 - step : step;
-        const int cur = step & 1;
-        const T* hcur = hbuf0 + cur * SROWS * HP;
-        T* hnxt = hbuf0 + (cur ^ 1) * SROWS * HP;
-        const T* xcur = xbuf + cur * SROWS * XIP + r * XIP;
-        FX_STAMP(step, 0);
-        sf32x16 acc[2];
-#pragma unroll
-        for (int blk = 0; blk < 2; ++blk)
-#pragma unroll
-            for (int gs = 0; gs < 2; ++gs)
-#pragma unroll
-                for (int qq = 0; qq < 2; ++qq) {
-                    const sf32x4 bv = *reinterpret_cast<const sf32x4*>(bsm + (2 * blk + gs) * SH + 16 * w8 + 8 * qq + 4 * hh);
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) acc[blk][8 * gs + 4 * qq + j] = bv[j];
-                }
-        {
-            constexpr int NK = XI / 16, NKR = X8RK / 16, DEPTH = 4;
-            sbf16x8 ring[DEPTH];
-#pragma unroll
-            for (int i = 0; i < DEPTH; ++i) ring[i] = *reinterpret_cast<const sbf16x8*>(xcur + i * 16 + 8 * hh);
-#pragma unroll
-#ifdef DIC_FWDX_EXP_NOPROJ
-            for (int ks = 0; ks < 1; ++ks) {
-#else
-            for (int ks = 0; ks < NK; ++ks) {
-#endif
-                if (ks < NKR) {
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wx[0][ks], ring[ks % DEPTH], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wx[1][ks], ring[ks % DEPTH], acc[1], 0, 0, 0);
-                } else {
-                    const sbf16x8 a0 = *reinterpret_cast<const sbf16x8*>(wl + arow[0] * X8LP + (ks - NKR) * 16 + 8 * hh);
-                    const sbf16x8 a1 = *reinterpret_cast<const sbf16x8*>(wl + arow[1] * X8LP + (ks - NKR) * 16 + 8 * hh);
-                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, ring[ks % DEPTH], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, ring[ks % DEPTH], acc[1], 0, 0, 0);
-                }
-                if (ks + DEPTH < NK) ring[ks % DEPTH] = *reinterpret_cast<const sbf16x8*>(xcur + (ks + DEPTH) * 16 + 8 * hh);
-            }
-        }
-        FX_STAMP(step, 1);
-        {
-            sbf16x8 hf[SH / 16];
-#pragma unroll
-            for (int ks = 0; ks < SH / 16; ++ks) hf[ks] = *reinterpret_cast<const sbf16x8*>(hcur + r * HP + ks * 16 + 8 * hh);
-#pragma unroll
-            for (int ks = 0; ks < SH / 16; ++ks) {
-                acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[0][ks], hf[ks], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[1][ks], hf[ks], acc[1], 0, 0, 0);
-            }
-        }
-        FX_STAMP(step, 2);
-#ifndef DIC_FWDX_EXP_NOXLOAD
-        if (step + 1 < R) land_x(cur ^ 1);               // the x tile of the next step -> the other buffer (nobody reads it during this step)
-        if (step + 2 < R) load_x(step + 2);
-#endif
-        const bool last = step == R - 1;
-        const size_t row = (size_t)t * B + bc;
-        FX_STAMP(step, 3);
-        V4 cb0 = {}, hb0 = {};
-        sf32x4 hv0 = {0.f, 0.f, 0.f, 0.f};
+    int cur = 0;                     // the LDS buffer of the current step's h and x: alternates step by step, across tile boundaries too
+    for (int bt = blockIdx.x; bt < nbt; bt += W) {
+        // (the lane's row and half as the tile's addresses see them: opaque, or every global address is split into a part per kernel and a part per tile,
+        //  both held in registers through the step loop: 8 registers more than there are)
+        int rt = r, ht = hh;
+        asm volatile("" : "+v"(rt), "+v"(ht));
+        const int b = bt * SROWS + rt;
+        const bool ok = b < B;           // (only the last tiles of a direction are ragged)
+        const int bc = min(b, B - 1);
+        // h0 -> the current h buffer.  The closing barrier of the previous tile's last step lies between that tile's last read of either buffer and this
+        // write (its last step wrote its own h_R here: the same lanes to the same addresses, in program order).
+        float c[8];                      // element e = 4 qq + j: unit 16 w8 + 8 qq + 4 hh + j
 #pragma unroll
         for (int qq = 0; qq < 2; ++qq) {
-            const int u = 16 * w8 + 8 * qq + 4 * hh, q = 2 * qh + qq;
-            V4 hb, ib, fb, gb, ob, cb;
-            sf32x4 cv, hv;
+            const int u = 16 * w8 + 8 * qq + 4 * hh, ug = 16 * w8 + 8 * qq + 4 * ht;
+            sf32x4 hv = {0.f, 0.f, 0.f, 0.f}, cv = {0.f, 0.f, 0.f, 0.f};
+            if (ok) {
+                if (a.h0) hv = *reinterpret_cast<const sf32x4*>(a.h0 + sstate_off(a.bm, dir, b, B) + ug);
+                if (a.c0) cv = *reinterpret_cast<const sf32x4*>(a.c0 + sstate_off(a.bm, dir, b, B) + ug);
+            }
+            V4 hb;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int k = 4 * qq + j;
-#ifdef DIC_FWDX_EXP_NOGATE
-                const float ig = acc[0][k], fg = acc[0][8 + k], gg = acc[1][k], og = acc[1][8 + k];
-                const float cn = c[k] + ig, hn = og;
-#else
-                const float ig = fx_sigmoid(acc[0][k]), fg = fx_sigmoid(acc[0][8 + k]), gg = fx_tanh(acc[1][k]), og = fx_sigmoid(acc[1][8 + k]);
-                const float cn = fmaf(fg, c[k], ig * gg);
-                const float hn = og * fx_tanh(cn);
-#endif
-                c[k] = cn;
-                cv[j] = cn; hv[j] = hn;
-                hb[j] = (T)hn; ib[j] = (T)ig; fb[j] = (T)fg; gb[j] = (T)gg; ob[j] = (T)og; cb[j] = (T)cn;
-            }
-            *reinterpret_cast<V4*>(hnxt + r * HP + u) = hb;
-            // ---- stores, 16 B per lane (round 5).  Eight-byte stores cap a CU at ~7 B per cycle (store issue, MI355X_MICROARCH.md: the epilogue store
-            // tail) and this kernel writes 5.9: cycle stamps show the second wave of every SIMD stuck in its store phase.  The lane-native layout keeps a
-            // lane's four elements of a (gate, block) piece at slot (hh, r) of a 512-B piece, so NEIGHBOURING lanes hold neighbouring 8-B slots: lanes
-            // 2 i and 2 i + 1 trade (one quad-permute per dword) so that the even lane holds both lanes' values of piece A (16 B at its own slot) and the odd
-            // lane both lanes' values of piece B (16 B at the even lane's slot of B): one 16-B store per lane covers two whole pieces.  Same bytes, same
-            // addresses as the two 8-B stores it replaces.
-            if (a.gates) {
-                const size_t g0 = snative_off(t, nbt, bt, dir, w4, 4, 0, q, 0, 0), c0o = snative_off(t, nbt, bt, dir, w4, 1, 0, 2 * qh, 0, 0);
-                pair_store(a.gates + g0, ib, fb, 1024);                    // gates i | f: pieces 1024 elements apart
-                pair_store(a.gates + g0 + 2 * 1024, gb, ob, 1024);         // gates g | o
-                if (qq == 0) cb0 = cb;
-                else pair_store(a.cs + c0o, cb0, cb, 256);                 // cell state of blocks 0 | 1: pieces 256 elements apart
-            }
-            if (qq == 0) { hb0 = hb; hv0 = hv; }
-            else if (ok) {
-                // output rows: the halves of a wave hold units +0..3 / +4..7 (block 0) and +8..11 / +12..15 (block 1) of the same row: one
-                // v_permlane32_swap per dword makes that +0..7 in the lower half and +8..15 in the upper one
-                auto out16 = [&](T* base, V4 lo, V4 hi) {
-                    typedef unsigned su32x2 __attribute__((ext_vector_type(2)));
-                    const su32x2 x = __builtin_bit_cast(su32x2, lo), y = __builtin_bit_cast(su32x2, hi);
-                    const auto s0 = __builtin_amdgcn_permlane32_swap(x[0], y[0], false, false);      // x of lanes 32..63 <-> y of lanes 0..31
-                    const auto s1 = __builtin_amdgcn_permlane32_swap(x[1], y[1], false, false);
-                    uint4 v;
-                    v.x = s0[0]; v.y = s1[0]; v.z = s0[1]; v.w = s1[1];
-                    *reinterpret_cast<uint4*>(base + row * 2 * SH + dir * SH + 16 * w8 + 8 * hh) = v;
-                };
-                out16(a.out, hb0, hb);
-                if (a.out_r) {
-                    V4 hr0, hr1;
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) { hr0[j] = (T)fmaxf(hv0[j], 0.f); hr1[j] = (T)fmaxf(hv[j], 0.f); }
-                    out16(a.out_r, hr0, hr1);
-                }
-            }
-            if (ok && last) {
-                *reinterpret_cast<sf32x4*>(a.hn + sstate_off(a.bm, dir, b, B) + u) = hv;
-                *reinterpret_cast<sf32x4*>(a.cn + sstate_off(a.bm, dir, b, B) + u) = cv;
+            for (int j = 0; j < 4; ++j) { hb[j] = (T)hv[j]; c[4 * qq + j] = cv[j]; }
+            *reinterpret_cast<V4*>(hbuf0 + cur * SROWS * HP + r * HP + u) = hb;
+            if (a.boundary && ok) {
+                T* slot = dir ? a.out + (size_t)R * B * 2 * SH : a.out - (size_t)B * 2 * SH;
+                *reinterpret_cast<V4*>(slot + (size_t)b * 2 * SH + dir * SH + ug) = hb;
             }
         }
-        FX_STAMP(step, 4);
-        lds_barrier();
-        FX_STAMP(step, 5);
+        lds_barrier();                   // h0 is in place (first tile: the weight images, the bias and the first x tile too; LDS traffic only, so no drain)
+        if (bt == (int)blockIdx.x) FX_STAMP_WG(1);
+        for (int step = 0; step < R; ++step, cur ^= 1) {
+            const int t = dir ? R - 1 - step : step;
+            const T* hcur = hbuf0 + cur * SROWS * HP;
+            T* hnxt = hbuf0 + (cur ^ 1) * SROWS * HP;
+            const T* xcur = xbuf + cur * SROWS * XIP + r * XIP;
+            FX_STAMP(step, 0);
+            sf32x16 acc[2];
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+                for (int gs = 0; gs < 2; ++gs)
+#pragma unroll
+                    for (int qq = 0; qq < 2; ++qq) {
+                        const sf32x4 bv = *reinterpret_cast<const sf32x4*>(bsm + (2 * blk + gs) * SH + 16 * w8 + 8 * qq + 4 * hh);
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) acc[blk][8 * gs + 4 * qq + j] = bv[j];
+                    }
+            {
+                constexpr int NK = XI / 16, NKR = X8RK / 16, DEPTH = 4;
+                sbf16x8 ring[DEPTH];
+#pragma unroll
+                for (int i = 0; i < DEPTH; ++i) ring[i] = *reinterpret_cast<const sbf16x8*>(xcur + i * 16 + 8 * hh);
+#pragma unroll
+#ifdef DIC_FWDX_EXP_NOPROJ
+                for (int ks = 0; ks < 1; ++ks) {
+#else
+                for (int ks = 0; ks < NK; ++ks) {
+#endif
+                    if (ks < NKR) {
+                        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wx[0][ks], ring[ks % DEPTH], acc[0], 0, 0, 0);
+                        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wx[1][ks], ring[ks % DEPTH], acc[1], 0, 0, 0);
+                    } else {
+                        const sbf16x8 a0 = *reinterpret_cast<const sbf16x8*>(wl + arow[0] * X8LP + (ks - NKR) * 16 + 8 * hh);
+                        const sbf16x8 a1 = *reinterpret_cast<const sbf16x8*>(wl + arow[1] * X8LP + (ks - NKR) * 16 + 8 * hh);
+                        acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, ring[ks % DEPTH], acc[0], 0, 0, 0);
+                        acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, ring[ks % DEPTH], acc[1], 0, 0, 0);
+                    }
+                    if (ks + DEPTH < NK) ring[ks % DEPTH] = *reinterpret_cast<const sbf16x8*>(xcur + (ks + DEPTH) * 16 + 8 * hh);
+                }
+            }
+            FX_STAMP(step, 1);
+            {
+                sbf16x8 hf[SH / 16];
+#pragma unroll
+                for (int ks = 0; ks < SH / 16; ++ks) hf[ks] = *reinterpret_cast<const sbf16x8*>(hcur + r * HP + ks * 16 + 8 * hh);
+#pragma unroll
+                for (int ks = 0; ks < SH / 16; ++ks) {
+                    acc[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[0][ks], hf[ks], acc[0], 0, 0, 0);
+                    acc[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh[1][ks], hf[ks], acc[1], 0, 0, 0);
+                }
+            }
+            FX_STAMP(step, 2);
+#ifndef DIC_FWDX_EXP_NOXLOAD
+            if (step + 1 < R || bt + W < nbt) land_x(cur ^ 1);       // the x tile of the next step (of the next tile after a tile's last step) -> the other
+            if (xbt < nbt) load_x();                                 // buffer (nobody reads it during this step); the one after it -> registers
+#endif
+            const bool last = step == R - 1;
+            const size_t row = (size_t)t * B + bc;
+            FX_STAMP(step, 3);
+            V4 cb0 = {}, hb0 = {};
+            sf32x4 hv0 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int qq = 0; qq < 2; ++qq) {
+                const int u = 16 * w8 + 8 * qq + 4 * hh, q = 2 * qh + qq;
+                V4 hb, ib, fb, gb, ob, cb;
+                sf32x4 cv, hv;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int k = 4 * qq + j;
+#ifdef DIC_FWDX_EXP_NOGATE
+                    const float ig = acc[0][k], fg = acc[0][8 + k], gg = acc[1][k], og = acc[1][8 + k];
+                    const float cn = c[k] + ig, hn = og;
+#else
+                    const float ig = fx_sigmoid(acc[0][k]), fg = fx_sigmoid(acc[0][8 + k]), gg = fx_tanh(acc[1][k]), og = fx_sigmoid(acc[1][8 + k]);
+                    const float cn = fmaf(fg, c[k], ig * gg);
+                    const float hn = og * fx_tanh(cn);
+#endif
+                    c[k] = cn;
+                    cv[j] = cn; hv[j] = hn;
+                    hb[j] = (T)hn; ib[j] = (T)ig; fb[j] = (T)fg; gb[j] = (T)gg; ob[j] = (T)og; cb[j] = (T)cn;
+                }
+                *reinterpret_cast<V4*>(hnxt + r * HP + u) = hb;
+                // ---- stores, 16 B per lane (round 5).  Eight-byte stores cap a CU at ~7 B per cycle (store issue, MI355X_MICROARCH.md: the epilogue store
+                // tail) and this kernel writes 5.9: cycle stamps show the second wave of every SIMD stuck in its store phase.  The lane-native layout keeps a
+                // lane's four elements of a (gate, block) piece at slot (hh, r) of a 512-B piece, so NEIGHBOURING lanes hold neighbouring 8-B slots: lanes
+                // 2 i and 2 i + 1 trade (one quad-permute per dword) so that the even lane holds both lanes' values of piece A (16 B at its own slot) and the odd
+                // lane both lanes' values of piece B (16 B at the even lane's slot of B): one 16-B store per lane covers two whole pieces.  Same bytes, same
+                // addresses as the two 8-B stores it replaces.
+                if (a.gates) {
+                    const size_t g0 = snative_off(t, nbt, bt, dir, w4, 4, 0, q, 0, 0), c0o = snative_off(t, nbt, bt, dir, w4, 1, 0, 2 * qh, 0, 0);
+                    pair_store(a.gates + g0, ib, fb, 1024);                    // gates i | f: pieces 1024 elements apart
+                    pair_store(a.gates + g0 + 2 * 1024, gb, ob, 1024);         // gates g | o
+                    if (qq == 0) cb0 = cb;
+                    else pair_store(a.cs + c0o, cb0, cb, 256);                 // cell state of blocks 0 | 1: pieces 256 elements apart
+                }
+                if (qq == 0) { hb0 = hb; hv0 = hv; }
+                else if (ok) {
+                    // output rows: the halves of a wave hold units +0..3 / +4..7 (block 0) and +8..11 / +12..15 (block 1) of the same row: one
+                    // v_permlane32_swap per dword makes that +0..7 in the lower half and +8..15 in the upper one
+                    auto out16 = [&](T* base, V4 lo, V4 hi) {
+                        typedef unsigned su32x2 __attribute__((ext_vector_type(2)));
+                        const su32x2 x = __builtin_bit_cast(su32x2, lo), y = __builtin_bit_cast(su32x2, hi);
+                        const auto s0 = __builtin_amdgcn_permlane32_swap(x[0], y[0], false, false);      // x of lanes 32..63 <-> y of lanes 0..31
+                        const auto s1 = __builtin_amdgcn_permlane32_swap(x[1], y[1], false, false);
+                        uint4 v;
+                        v.x = s0[0]; v.y = s1[0]; v.z = s0[1]; v.w = s1[1];
+                        *reinterpret_cast<uint4*>(base + row * 2 * SH + dir * SH + 16 * w8 + 8 * ht) = v;
+                    };
+                    out16(a.out, hb0, hb);
+                    if (a.out_r) {
+                        V4 hr0, hr1;
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) { hr0[j] = (T)fmaxf(hv0[j], 0.f); hr1[j] = (T)fmaxf(hv[j], 0.f); }
+                        out16(a.out_r, hr0, hr1);
+                    }
+                }
+                if (ok && last) {
+                    *reinterpret_cast<sf32x4*>(a.hn + sstate_off(a.bm, dir, b, B) + 16 * w8 + 8 * qq + 4 * ht) = hv;
+                    *reinterpret_cast<sf32x4*>(a.cn + sstate_off(a.bm, dir, b, B) + 16 * w8 + 8 * qq + 4 * ht) = cv;
+                }
+            }
+            FX_STAMP(step, 4);
+            lds_barrier();
+            FX_STAMP(step, 5);
+        }
     }
+    FX_STAMP_WG(2);
 }
 
 template <typename T>
@@ -1960,8 +1985,10 @@ int dic_lstm_fwd_xproj(const void* x, const void* wih, const void* whh, const vo
     DIC_REQUIRE((gates == nullptr) == (cs == nullptr), DIC_ERR_INVALID_ARG, "lstm_fwd_xproj: gates and cs go together");
     typedef __bf16 T;
     FwdXArgs a{(const T*)x, (const T*)wih, (const T*)whh, (const T*)bias, h0, c0, (T*)out, hn, cn, (T*)gates, (T*)cs, R, B,
-               (state_flags & 1) != 0, (state_flags & 2) != 0, relu_x != 0, (T*)out_r};
-    const dim3 grid(2 * ((B + 63) / 64), 2);       // 32-row tiles of a batch padded to 64 rows: the tile count dic_lstm_bwd indexes the saved state with
+               (state_flags & 1) != 0, (state_flags & 2) != 0, relu_x != 0, (T*)out_r, 0};
+    const int nbt = 2 * ((B + 63) / 64);            // 32-row tiles of a batch padded to 64 rows: the tile count dic_lstm_bwd indexes the saved state with
+    a.nbt = nbt;
+    const dim3 grid(max(1, min(nbt, device_cus() / 2)), 2);     // persistent: one workgroup per CU walks the tiles of its direction
     const size_t lds = ((size_t)2 * SROWS * Rec<T>::PITCH(SH) + (size_t)2 * SROWS * XIP + (size_t)S4 * X8LP) * sizeof(T) + (size_t)S4 * sizeof(float);
     static bool attr_set = false;
     if (!attr_set) {

@@ -38,16 +38,6 @@ struct RowProjArgs {
                            // F.relu between the two), rectified on its way into LDS -- no rectified copy of the encoder output in HBM
 };
 
-// relu of packed bf16 pairs as ONE integer instruction per register: a negative bf16 is a negative int16, so max(x, 0) on the 16-bit
-// halves (v_pk_max_i16) zeroes exactly the negative halves (and -0.0); `floor` = 0 applies it, 0x8000 per half (INT16_MIN) is the identity
-typedef short ps16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_relu(unsigned x, unsigned floor) {
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(ps16x2, x), __builtin_bit_cast(ps16x2, floor)));
-}
-__device__ __forceinline__ uint4 pk_relu4(uint4 v, unsigned floor) {
-    return make_uint4(pk_relu(v.x, floor), pk_relu(v.y, floor), pk_relu(v.z, floor), pk_relu(v.w, floor));
-}
-
 // NATIVE (the decoder's gx, Nout = 1024 = 2 directions x 4 gates x 128 units, read back only by the recurrence kernel): the product is
 // issued TRANSPOSED -- D[output column][row] = W . x^T, the same fragments with the operands swapped -- so lane (row r, hh) ends up
 // with the 16 pre-activations the recurrence kernel's lane (r, hh) of wave (column / 32) % 4 wants in its accumulators, and writes

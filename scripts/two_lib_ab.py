@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Interleaved A/B of one entry point between TWO builds of libdic_hip.so in one process (boxes drift by several per cent within a run, so builds are
-timed alternately, several rounds): DIC_AB_LIB=<second .so> python3 scripts/two_lib_ab.py {fwd_proj|fwd_xproj|bwd|dx} [B] [rounds]"""
+timed alternately, several rounds; the first `warm` alternations, while clocks and caches settle, are shown but not counted):
+DIC_AB_LIB=<second .so> python3 scripts/two_lib_ab.py {fwd_proj|fwd_xproj|bwd|dx} [B] [rounds] [warm]"""
 import ctypes as C
 import os
 import sys
@@ -14,6 +15,7 @@ from deep_interpolation_clustering_amd import _native as N  # noqa: E402
 what = sys.argv[1] if len(sys.argv) > 1 else 'fwd_proj'
 B = int(sys.argv[2]) if len(sys.argv) > 2 else 32768
 rounds = int(sys.argv[3]) if len(sys.argv) > 3 else 6
+warm = int(sys.argv[4]) if len(sys.argv) > 4 else 2
 LA = N.lib()
 LB = C.CDLL(os.path.abspath(os.environ['DIC_AB_LIB']))
 for name, (res, args) in N.SIGNATURES.items():
@@ -72,8 +74,11 @@ a(); sa = chk()
 b(); sb = chk()
 print('checksums A', sa, 'B', sb)
 ta, tb = [], []
-for _ in range(rounds):
+for _ in range(warm + rounds):
     ta.append(bench.time_kernel(a, 10) * 1e3)
     tb.append(bench.time_kernel(b, 10) * 1e3)
+print(what, 'B = %d, warm-up alternations (not counted): A' % B, ' '.join('%.1f' % t for t in ta[:warm]), ' B', ' '.join('%.1f' % t for t in tb[:warm]))
+ta, tb = ta[warm:], tb[warm:]
 print(what, 'A (in-tree lib) us:', ' '.join('%.1f' % t for t in ta), ' median %.1f' % sorted(ta)[len(ta) // 2])
 print(what, 'B (DIC_AB_LIB)  us:', ' '.join('%.1f' % t for t in tb), ' median %.1f' % sorted(tb)[len(tb) // 2])
+print(what, 'slowest A %.1f %s fastest B %.1f' % (max(ta), '<' if max(ta) < min(tb) else '>=', min(tb)))
