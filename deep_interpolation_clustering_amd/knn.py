@@ -5,6 +5,11 @@ that curve from ``kneed.KneeLocator(point_num, sorted_dist, S=1.0, curve='convex
 csrc/dic_knn.hip: counting passes of the DBSCAN tile machine with per-row thresholds narrow every row's k-th distance to a short candidate list, and the
 value at the exact rank is taken from f64 difference-form distances of the candidates.  The convention is upstream's: the point itself is its own first
 neighbour (k = 1 gives 0, duplicates give zeros).  The same quantity is OPTICS' core distance (``core_distances``): optics.py builds on it.
+
+Neighbour LISTS come from the same file (``dic_knn_neighbors``): ``kneighbors`` gives, for every query, its k nearest index points sorted by (distance, index),
+of a set against itself or of a query set against an index set; ``NearestNeighbors`` wraps it in sklearn's interface (``kneighbors``, ``kneighbors_graph`` as
+CSR triples), and ``knn_transfer_labels`` is the uniform vote of ``KNeighborsClassifier`` -- the out-of-sample labels p4 gives DBSCAN and HDBSCAN with
+``--transfer knn``.
 """
 from __future__ import annotations
 
@@ -62,6 +67,144 @@ def kth_neighbor_distance(X, k, candidate_budget=None, stats=None):
         raise CandidateBudgetError('kth_neighbor_distance: %s' % L.dic_last_error_string().decode(), st[4])
     N.check(rc, 'dic_knn_kth_distance')
     return out.cpu().numpy()
+
+
+MAX_NEIGHBORS = 1024          # csrc/dic_knn.hip: KN_MAXK, the rows the exact stage sorts in LDS
+
+
+def _check_k(k, n_fit, n_queries, query_is_train=False):
+    """sklearn's wording (neighbors/_base.py, KNeighborsMixin.kneighbors); ``k`` already counts the extra neighbour of ``query_is_train``."""
+    if k - int(query_is_train) <= 0:
+        raise ValueError('Expected n_neighbors > 0. Got %d' % (k - int(query_is_train)))
+    if k > n_fit:
+        raise ValueError('Expected %s, but n_neighbors = %d, n_samples_fit = %d, n_samples = %d' % (
+            'n_neighbors < n_samples_fit' if query_is_train else 'n_neighbors <= n_samples_fit', k - int(query_is_train), n_fit, n_queries))
+    if k > MAX_NEIGHBORS:
+        raise NotImplementedError('kneighbors: at most %d neighbours (got %d)' % (MAX_NEIGHBORS, k))
+
+
+def kneighbors(X, k, Q=None, candidate_budget=None, stats=None, return_device=False):
+    """``(dist (M, k) float64, idx (M, k) int32)``: for every row of ``Q`` (every row of ``X`` when ``Q`` is None: the self join, the row itself included
+    as an ordinary neighbour at distance 0) the k rows of ``X`` with the smallest (distance, index), in that order --
+    ``NearestNeighbors(n_neighbors=k, algorithm='brute').fit(X).kneighbors(Q)``, but exact for the f32 coordinates (f64 difference form) and with ties in
+    distance settled by the smaller index.  ``X`` (N, D) and ``Q`` (M, D): numpy arrays or tensors, D <= 256, k <= min(N, 1024).  numpy results, or device
+    tensors with ``return_device=True``.  ``candidate_budget`` and ``stats`` as for ``kth_neighbor_distance``: the budget never changes the result.  The
+    approximate products that narrow the search are centred on the mean of ``X``: queries far from the index points get longer candidate lists -- the same
+    result, but a distant query cohort may need a larger ``candidate_budget`` (``CandidateBudgetError.needed`` says how large)."""
+    n, dx = _shape_of(X)
+    m = n
+    if Q is not None:
+        m, dq = _shape_of(Q)
+        if dq != dx:
+            raise ValueError('X has %d features, but NearestNeighbors is expecting %d features as input.' % (dq, dx))
+    if n < 1 or m < 1:
+        raise ValueError('Found array with 0 sample(s) (shape=(%d, %d)) while a minimum of 1 is required.' % (min(n, m), dx))
+    k = int(k)
+    _check_k(k, n, m)
+    budget = 0 if candidate_budget is None else int(candidate_budget)
+    if candidate_budget is not None and budget < 1:
+        raise ValueError('candidate_budget must be positive, got %r' % (candidate_budget,))
+    if dx > MAX_DIM:
+        raise NotImplementedError('kneighbors: at most %d features (got %d)' % (MAX_DIM, dx))
+    x = _device_points(X)
+    q = None
+    if Q is not None:
+        q = _device_points(Q).to(x.device)
+    d = x.shape[1]
+    L = N.lib()
+    ws = torch.empty(max(16, L.dic_knn_neighbors_workspace(n, 0 if q is None else m, d, budget)), dtype=torch.uint8, device=x.device)
+    dist = torch.empty((m, k), dtype=torch.float64, device=x.device)
+    idx = torch.empty((m, k), dtype=torch.int32, device=x.device)
+    centre = x.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
+    st = (N.C.c_int64 * len(STAT_NAMES))()
+    rc = L.dic_knn_neighbors(N.ptr(x), x.stride(0), n, None if q is None else N.ptr(q), 0 if q is None else q.stride(0), 0 if q is None else m, N.ptr(centre), d,
+                             k, N.ptr(dist), N.ptr(idx), budget, st, N.ptr(ws), ws.numel(), N.stream_of(x))
+    if stats is not None:
+        stats.update(zip(STAT_NAMES, (int(v) for v in st)))
+    if rc == -3 and st[4] > 0:          # DIC_ERR_WORKSPACE: one list alone is longer than the budget
+        raise CandidateBudgetError('kneighbors: %s' % L.dic_last_error_string().decode(), st[4])
+    N.check(rc, 'dic_knn_neighbors')
+    if return_device:
+        return dist, idx
+    return dist.cpu().numpy(), idx.cpu().numpy()
+
+
+class NearestNeighbors:
+    """``sklearn.neighbors.NearestNeighbors(n_neighbors, algorithm='brute')`` for the euclidean metric, on ``kneighbors`` above."""
+
+    def __init__(self, n_neighbors=5):
+        self.n_neighbors = n_neighbors
+
+    def fit(self, X, y=None):
+        n, d = _shape_of(X)
+        if n < 1:
+            raise ValueError('Found array with 0 sample(s) (shape=(%d, %d)) while a minimum of 1 is required.' % (n, d))
+        if d > MAX_DIM:
+            raise NotImplementedError('NearestNeighbors: at most %d features (got %d)' % (MAX_DIM, d))
+        if int(self.n_neighbors) <= 0:
+            raise ValueError('Expected n_neighbors > 0. Got %d' % int(self.n_neighbors))
+        self._fit_X = X
+        self.n_samples_fit_, self.n_features_in_ = n, d
+        return self
+
+    def _fitted(self):
+        if not hasattr(self, '_fit_X'):
+            raise RuntimeError("This NearestNeighbors instance is not fitted yet. Call 'fit' with appropriate arguments before using this estimator.")
+
+    def kneighbors(self, X=None, n_neighbors=None, return_distance=True):
+        """``(dist, idx)`` (``idx`` alone with ``return_distance=False``).  ``X=None`` queries the fitted points and leaves each point out of its own list, as
+        sklearn 1.7.2 does it: k + 1 neighbours are taken and the entry whose index is the row's own is dropped; where the row's own index is not among
+        them (k + 1 or more duplicates of the point sort before it) the first column is dropped."""
+        self._fitted()
+        k = int(self.n_neighbors if n_neighbors is None else n_neighbors)
+        query_is_train = X is None
+        n = self.n_samples_fit_
+        if query_is_train:
+            _check_k(k + 1, n, n, query_is_train=True)
+            dist, idx = kneighbors(self._fit_X, k + 1)
+            keep = idx != np.arange(n, dtype=idx.dtype)[:, None]
+            keep[np.all(keep, axis=1), 0] = False
+            dist, idx = dist[keep].reshape(n, k), idx[keep].reshape(n, k)
+        else:
+            m, d = _shape_of(X)
+            if d != self.n_features_in_:
+                raise ValueError('X has %d features, but NearestNeighbors is expecting %d features as input.' % (d, self.n_features_in_))
+            _check_k(k, n, m)
+            dist, idx = kneighbors(self._fit_X, k, Q=X)
+        return (dist, idx) if return_distance else idx
+
+    def kneighbors_graph(self, X=None, n_neighbors=None, mode='connectivity'):
+        """The k-neighbour graph as the CSR triple ``(data (M k,) float64, indices (M k,) int32, indptr (M + 1,) int64)`` of an (M, n_samples_fit) matrix
+        -- ``scipy.sparse.csr_matrix((data, indices, indptr), shape=(M, n_samples_fit))`` is sklearn's ``kneighbors_graph``.  ``mode='connectivity'``: ones;
+        ``'distance'``: the distances."""
+        if mode not in ('connectivity', 'distance'):
+            raise ValueError('Unsupported mode, must be one of "connectivity", or "distance" but got "%s" instead' % (mode,))
+        dist, idx = self.kneighbors(X, n_neighbors)
+        m, k = idx.shape
+        data = np.ones(m * k, dtype=np.float64) if mode == 'connectivity' else np.ascontiguousarray(dist).ravel()
+        return data, np.ascontiguousarray(idx).ravel(), np.arange(0, m * k + 1, k, dtype=np.int64)
+
+
+def knn_transfer_labels(X_train, labels_train, Q, k, candidate_budget=None):
+    """``(labels (M,) int32, share (M,) float32)``: every row of ``Q`` takes the label most frequent among its k nearest rows of ``X_train`` --
+    ``KNeighborsClassifier(n_neighbors=k, algorithm='brute').fit(X_train, labels_train).predict(Q)``, uniform weights.  Every distinct label is a class,
+    -1 (noise) included; on equal votes the smallest label wins.  ``share`` is the winner's fraction of the k votes.  The vote runs on the device."""
+    n, _ = _shape_of(X_train)
+    y = np.asarray(labels_train)
+    if y.ndim != 1 or y.shape[0] != n:
+        raise ValueError('Found input variables with inconsistent numbers of samples: [%d, %d]' % (n, y.shape[0] if y.ndim else 0))
+    if not np.issubdtype(y.dtype, np.integer):
+        raise ValueError('labels_train must be integers, got %s' % y.dtype)
+    _, idx = kneighbors(X_train, k, Q=Q, candidate_budget=candidate_budget, return_device=True)
+    classes, codes = np.unique(y, return_inverse=True)          # ascending: the first maximum below is the smallest label
+    votes = torch.as_tensor(codes.astype(np.int64), device=idx.device)[idx.long()]          # (M, k) class codes
+    tally = torch.zeros((idx.shape[0], len(classes)), dtype=torch.int64, device=idx.device)
+    tally.scatter_add_(1, votes, torch.ones_like(votes))
+    best = tally.max(dim=1).values
+    win = (tally == best[:, None]).int().argmax(dim=1)          # argmax returns the FIRST maximal index (documented by torch): of the classes at the maximum, the smallest label
+    labels = classes[win.cpu().numpy()].astype(np.int32)
+    share = (best.float() / float(idx.shape[1])).cpu().numpy().astype(np.float32)
+    return labels, share
 
 
 def core_distances(X, min_samples, candidate_budget=None, stats=None):

@@ -11,6 +11,11 @@ provide here: it raises.  (p2's optics branch exists: optics.py.)
 ``hdbscan`` (no upstream counterpart; the dbscan branch without its eps): an HDBSCAN(min_cluster_size = --hdbscan_min_cluster_size, default feat_dim + 1,
 min_samples = feat_dim + 1) fit per cohort on the GPU (hdbscan.py), training clusters re-numbered by sbp, validation / test clusters mapped onto the nearest
 training centre, exactly as the dbscan branch does it; writes <cohort>_mcs-<min_cluster_size>.npy.
+``--transfer knn`` (dbscan and hdbscan; no upstream counterpart): only the training cohort is fitted and re-numbered by sbp; every validation / test
+encounter takes the label most frequent among its --transfer_k (default feat_dim + 1) nearest training encounters, noise being a label like any other
+(knn.knn_transfer_labels: the vote of KNeighborsClassifier).  That works whatever the cohorts' own cluster counts would have been and labels a non-convex
+cluster by its members, not its centre.  Writes <cohort>_eps-<opt_eps>_knn.npy / <cohort>_mcs-<min_cluster_size>_knn.npy with ``cluster_id`` and
+``cluster_vote``, the winning label's share of the votes (1 for the training cohort).  The default, ``--transfer centre``, is the behaviour above.
 ``consensus`` (p4:241-287): reads the raw consensus labels of out_feat/raw_consensus_result/<cohort>_consensus.csv (column k<num_clusters>, 0- or 1-based),
 re-numbers the training clusters by sbp (generate_align_map) and applies that map to the training and the validation cohort (upstream leaves the test cohort
 out); writes <cohort>_<k>.npy.  Upstream's csv files were "generated outside"; a missing one is first computed here by consensus clustering of that cohort's
@@ -36,6 +41,7 @@ from .gmm import GaussianMixture
 from .hdbscan import HDBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
+from .knn import knn_transfer_labels
 from .utils import logger, print_dict_byline
 from .ward import Ward
 
@@ -49,6 +55,10 @@ def get_arguments(argv=None):
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
     p.add_argument('--hdbscan_min_cluster_size', type=int, default=None, help='(extra) min_cluster_size of --cluster_method hdbscan; default feat_dim + 1')
+    p.add_argument('--transfer', default='centre', choices=['centre', 'knn'],
+                   help="(extra) how --cluster_method dbscan / hdbscan label the validation and test cohorts: 'centre' fits each cohort and maps its clusters onto "
+                        "the nearest training centre (upstream); 'knn' fits the training cohort only and votes among the nearest training encounters")
+    p.add_argument('--transfer_k', type=int, default=None, help='(extra) neighbours of --transfer knn; default feat_dim + 1')
     p.add_argument('--dl_cluster_label_type', default='pred', choices=['label', 'pred'])
     return p.parse_args(argv)
 
@@ -103,26 +113,50 @@ class Cluster(object):
             org_label[members[org_id]] = new_id
         return org_label
 
+    def _knn_labels(self, f_train, train_ref, feat):
+        """--transfer knn: ``(cluster_id, cluster_vote)`` of a validation / test cohort from the training latents and their aligned labels -- ``train_ref``
+        as the training cohort left it in this run, else read back from the training file ``f_train`` of an earlier one."""
+        if train_ref is None:
+            if not osp.exists(f_train):
+                raise ValueError('--transfer knn: the training cohort has no labels to transfer (no cluster was found, or {} is missing)'.format(f_train))
+            done = np.load(f_train, allow_pickle=True).item()
+            train_ref = (done['hidden'], done['cluster_id'])
+        k = self.args.transfer_k if getattr(self.args, 'transfer_k', None) is not None else self.feat_dim + 1
+        logger.info('kNN label transfer from {} training encounters, k: {}'.format(len(train_ref[1]), k))
+        label, vote = knn_transfer_labels(train_ref[0], np.asarray(train_ref[1]).astype(np.int64), feat, k)
+        return label.astype(np.asarray(train_ref[1]).dtype), vote
+
     def _dbscan(self, cohorts, overwrite):
         opt_eps = self.args.opt_eps
         logger.info('==> Generate the DBSCAN results with opt-eps: {}'.format(opt_eps))
         train_feat_centers = None
+        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
+        name = '{}_eps-{}_knn.npy' if knn else '{}_eps-{}.npy'
+        train_ref = None
         for cohort, data in cohorts:
-            f = osp.join(self.out_path, '{}_eps-{}.npy'.format(cohort, opt_eps))
+            f = osp.join(self.out_path, name.format(cohort, opt_eps))
             if osp.exists(f) and not overwrite:
                 logger.info('Not Save for {}.'.format(f))
                 continue
-            logger.info('NEW DBSCAN model for {}'.format(cohort))
             feat = data['hidden']
-            db = DBSCAN(opt_eps, feat.shape[-1]).fit(feat)
-            raw_label = db.labels_
-            if cohort == 'training':
-                _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
+            if knn and cohort != 'training':
+                aligned_label, data['cluster_vote'] = self._knn_labels(osp.join(self.out_path, name.format('training', opt_eps)), train_ref, feat)
+                db = None
             else:
-                aligned_label = self.align_labels_with_center(feat, raw_label, train_feat_centers)
+                logger.info('NEW DBSCAN model for {}'.format(cohort))
+                db = DBSCAN(opt_eps, feat.shape[-1]).fit(feat)
+                raw_label = db.labels_
+                if cohort == 'training':
+                    _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
+                else:
+                    aligned_label = self.align_labels_with_center(feat, raw_label, train_feat_centers)
+                if knn:
+                    train_ref = (feat, aligned_label)
+                    data['cluster_vote'] = np.ones(len(aligned_label), dtype=np.float32)
             data['cluster_id'] = aligned_label
             del data['ob'], data['padding_mask']
-            logger.info('core_sample: {}'.format(len(db.core_sample_indices_)))
+            if db is not None:
+                logger.info('core_sample: {}'.format(len(db.core_sample_indices_)))
             n_clusters_ = len(set(aligned_label)) - (1 if -1 in aligned_label else 0)
             n_noise_ = int(np.sum(aligned_label == -1))
             keep = aligned_label != -1
@@ -144,18 +178,27 @@ class Cluster(object):
         mcs = self.args.hdbscan_min_cluster_size if self.args.hdbscan_min_cluster_size is not None else self.feat_dim + 1
         logger.info('==> Generate the HDBSCAN results with min_cluster_size: {}, min_samples: {}'.format(mcs, min_samples))
         train_feat_centers = None
+        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
+        name = '{}_mcs-{}_knn.npy' if knn else '{}_mcs-{}.npy'
+        train_ref = None
         for cohort, data in cohorts:
-            f = osp.join(self.out_path, '{}_mcs-{}.npy'.format(cohort, mcs))
+            f = osp.join(self.out_path, name.format(cohort, mcs))
             if osp.exists(f) and not overwrite:
                 logger.info('Not Save for {}.'.format(f))
                 continue
-            logger.info('NEW HDBSCAN model for {}'.format(cohort))
             feat = data['hidden']
-            raw_label = HDBSCAN(min_cluster_size=mcs, min_samples=min_samples).fit(feat).labels_
-            if cohort == 'training':
-                _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
+            if knn and cohort != 'training':
+                aligned_label, data['cluster_vote'] = self._knn_labels(osp.join(self.out_path, name.format('training', mcs)), train_ref, feat)
             else:
-                aligned_label = self.align_labels_with_center(feat, raw_label, train_feat_centers)
+                logger.info('NEW HDBSCAN model for {}'.format(cohort))
+                raw_label = HDBSCAN(min_cluster_size=mcs, min_samples=min_samples).fit(feat).labels_
+                if cohort == 'training':
+                    _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
+                else:
+                    aligned_label = self.align_labels_with_center(feat, raw_label, train_feat_centers)
+                if knn:
+                    train_ref = (feat, aligned_label)
+                    data['cluster_vote'] = np.ones(len(aligned_label), dtype=np.float32)
             data['cluster_id'] = aligned_label
             del data['ob'], data['padding_mask']
             n_clusters_ = len(set(aligned_label)) - (1 if -1 in aligned_label else 0)
@@ -271,6 +314,10 @@ class Cluster(object):
 
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)
+        transfer = getattr(self.args, 'transfer', 'centre')          # (an args object from before the flag: the default)
+        if transfer != 'centre' and self.args.cluster_method not in ('dbscan', 'hdbscan'):
+            raise ValueError("--transfer {} applies to --cluster_method dbscan and hdbscan only: '{}' labels every cohort with its training model "
+                             "already".format(transfer, self.args.cluster_method))
         for metric in self.args.restore_metric:
             self.feat_path = osp.join(self.exp_path, 'out_feat', metric)
             self.out_path = osp.join(self.exp_path, 'out_feat', '{}_{}'.format(metric, self.args.cluster_method)) + '_aligned'

@@ -628,6 +628,24 @@ size_t dic_knn_workspace(int64_t N, int D, int64_t candidate_budget);
 int dic_knn_kth_distance(const float* X, long ldx, const float* centre, int64_t N, int D, int64_t k, double* kth, int64_t candidate_budget, int64_t* stats,
                          void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* Exact k-nearest-neighbour lists without the distance matrix (csrc/dic_knn.hip): NearestNeighbors(n_neighbors=k, algorithm='brute').fit(X).kneighbors(Q), the
+ * lists knn.py's kneighbors, NearestNeighbors and knn_transfer_labels (p4's --transfer knn) are built on.  X (N, D) f32, row stride ldx: the index points;
+ * Q (M, D) f32, row stride ldq: the queries, or NULL for the self join (every index point queries; M and ldq ignored).  centre (1, D) f32 = the mean of
+ * the index points (any point near the data: it conditions the approximate products and never reaches the result).  D <= 256, D % 4 == 0, ldx % 4 == 0,
+ * ldq % 4 == 0, 1 <= k <= min(N, 1024), N + M < 2^30, X, Q, centre and the workspace 16-B aligned -- the rules of dic_knn_kth_distance.
+ *   dic_knn_neighbors: dist (M or N, k) f64 and idx (M or N, k) int32, DEVICE, OVERWRITTEN.  Row q holds the k index points j with the smallest keys
+ *       (d^2(q, j), j) in lexicographic order, sorted ascending by that key: d^2 = the f64 difference-form squared distance of the f32 coordinates (the
+ *       quantity dic_knn_kth_distance ranks, csrc/dic_exactd2.h), dist = its f64 square root, ties in distance broken by the smaller index.  The self pair of
+ *       a self join is an ordinary pair with d^2 = 0; a query is never a neighbour.  dist[:, k - 1] of the self join is dic_knn_kth_distance's result bit
+ *       for bit.  Nothing M x N is stored: four counting pair passes over the query row blocks x index column blocks bracket every row's k-th distance, one
+ *       more pair pass lists every index point the bracket cannot exclude (k plus a few on ordinary data, up to N with duplicates), and one workgroup per
+ *       row computes the exact d^2 of its list, radix-selects the key of rank k, and sorts the k survivors in LDS.  candidate_budget, stats and the
+ *       DIC_ERR_WORKSPACE protocol are dic_knn_kth_distance's (12 bytes per list entry; the result does not depend on the budget).  Reads list sizes back:
+ *       synchronises `stream`.  Two calls give the same bits. */
+size_t dic_knn_neighbors_workspace(int64_t N, int64_t M, int D, int64_t candidate_budget);
+int dic_knn_neighbors(const float* X, long ldx, int64_t N, const float* Q, long ldq, int64_t M, const float* centre, int D, int k, double* dist, int32_t* idx,
+                      int64_t candidate_budget, int64_t* stats, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 /* OPTICS' ordering without the distance matrix (csrc/dic_optics.hip): p2_clustering_optK.py:86-88,171-223 fits sklearn.cluster.OPTICS; this is its main loop
  * in the self-consistent form sklearn has with metric='precomputed' on the f64 difference-form distances d of the f32 points.  X, ldx, N, D as for
  * dic_knn_kth_distance (D <= 256, D % 4 == 0, N < 2^30, X and the workspace 16-B aligned).  core (N) f64, DEVICE, in: the core distances, already set to inf
