@@ -45,6 +45,14 @@ lower bound, BIC and AIC of the fit itself -- a likelihood-based criterion for K
 validation cohort and the --internal_metrics of the hard labels go to <metric>_gmm_aligned/plot/gmm_k.csv, the 0-based labels to plot/gmm_labels.csv, one
 column k<K> per K.
 
+``--cluster_method snn`` (no upstream counterpart): shared-nearest-neighbour clustering of the training latents on the GPU (snn.py: the k-neighbour lists of
+knn.py, one pass over them for the similarities, no N x N matrix) -- closeness counted in shared neighbours, an integer without a scale, where the euclidean
+eps of the dbscan branch flips from all noise to one cluster within a narrow band.  ONE graph with k = --snn_k (default feat_dim + 1) serves every
+--snn_eps (default round(k t / 10) for t = 2..8) at --snn_min_samples (default k // 4); the per-eps table -- the dbscan branch's columns plus k and
+min_samples -- goes to <metric>_snn_aligned/plot/snn_eps.csv, the list entries per similarity 0..k -- the curve eps is read from, as the k-distance graph is
+for DBSCAN -- to plot/snn_similarity_hist.csv (similarity, pairs) and the labels to plot/snn_labels.csv, one column eps<eps> per eps.  The defaults of
+--snn_eps and --snn_min_samples are starting points: nobody has measured them on the real latents.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -67,6 +75,7 @@ from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
 from .kmeans import KMeans, seed_draw_count
 from .knn import k_distance_graph
 from .optics import OPTICS
+from .snn import snn_sweep
 from .utils import logger, print_dict_byline
 from .ward import Ward as WardLinkage
 
@@ -75,7 +84,7 @@ np.random.seed(123)        # p2_clustering_optK.py:23
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn'])
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -89,6 +98,13 @@ def get_arguments(argv=None):
     p.add_argument('--hdbscan_min_cluster_size', type=int, nargs='+', default=None,
                    help='(extra) min_cluster_size values of --cluster_method hdbscan; default feat_dim + 1')
     p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical'], help='(extra) covariances of --cluster_method gmm')
+    p.add_argument('--snn_k', type=int, default=None, help='(extra) neighbours per point of --cluster_method snn; default feat_dim + 1')
+    p.add_argument('--snn_eps', type=int, nargs='+', default=None,
+                   help='(extra) shared-neighbour thresholds of --cluster_method snn, integers in [1, k]; default round(k t / 10) for t = 2..8 -- a starting '
+                        'point, not measured on the real latents: read eps from plot/snn_similarity_hist.csv')
+    p.add_argument('--snn_min_samples', type=int, default=None,
+                   help='(extra) strong links that make a core point of --cluster_method snn (0: Jarvis-Patrick); default k // 4 -- a starting point, not '
+                        'measured on the real latents')
     p.add_argument('--metric_sample', type=int, default=0, help='(extra) subsample size for the O(N^2) validity indices; 0 = all')
     return p.parse_args(argv)
 
@@ -396,6 +412,64 @@ class Dbscan(object):
             rows.append([float(eps), len(core), n_clusters_, n_noise_, sil, sil_dn])
         df = pd.DataFrame(rows, columns=self.COLUMNS)
         df.to_csv(osp.join(self.out_path, 'dbscan_eps.csv'), index=False)
+        return df
+
+
+def snn_default_eps(k):
+    """round(k t / 10) for t = 2..8, deduplicated, inside [1, k]: p2's default --snn_eps (a starting point: not measured on the real latents)."""
+    return sorted({min(k, max(1, int(round(k * t / 10.0)))) for t in range(2, 9)})
+
+
+class Snn(object):
+    """One shared-neighbour graph of the training latents (``snn.snn_sweep``: ``k`` neighbours) labelled once per eps of ``eps_values`` at ``min_samples``,
+    logged as Dbscan.train logs its fits.  Writes plot/snn_eps.csv (``COLUMNS``: Dbscan's, the silhouettes computed the same way, plus k and min_samples),
+    plot/snn_similarity_hist.csv (similarity 0..k, pairs: the list entries at that similarity, the self entries and the pairs that are not mutual at 0) and
+    plot/snn_labels.csv (one column eps<eps> per eps), and returns the per-eps table.  Existing files are left alone unless ``overwrite`` is set; the table
+    on disk is returned then.  ``labels_`` keeps the labels per eps of the last run that computed them, ``stats_`` that run's ``snn_sweep`` stats."""
+    COLUMNS = ['eps', 'n_core', 'n_clusters', 'n_noise', 'silhouette', 'denoise_silhouette', 'k', 'min_samples']
+    FILES = ('snn_eps.csv', 'snn_similarity_hist.csv', 'snn_labels.csv')
+
+    def __init__(self, k, eps_values, min_samples, out_path):
+        self.k, self.eps_values, self.min_sample = int(k), [int(e) for e in eps_values], int(min_samples)
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.labels_ = self.stats_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.labels_ = self.stats_ = None
+        eps_csv, hist_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (eps_csv, hist_csv, labels_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(eps_csv))
+            return pd.read_csv(eps_csv, float_precision='round_trip')          # (repr: exact)
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        stats = {}
+        fits = snn_sweep(Xd, self.k, self.eps_values, self.min_sample, stats=stats)
+        rows = []
+        for eps, (labels, core, _) in zip(self.eps_values, fits):
+            logger.info('\nRunning eps: {} (shared neighbours of {}), min_samples: {}'.format(eps, self.k, self.min_sample))
+            logger.info('core_sample: {}'.format(len(core)))
+            n_clusters_ = len(set(labels.tolist())) - (1 if -1 in labels else 0)
+            n_noise_ = int(np.sum(labels == -1))
+            logger.info('Estimated number of clusters: %d' % n_clusters_)
+            logger.info('Estimated number of noise points: %d' % n_noise_)
+            sil = sil_dn = float('nan')
+            if n_clusters_ == 1:
+                logger.info('Skip the Silhouette Coefficient calculation.')
+            elif n_clusters_ > 1:
+                keep = labels != -1
+                sil = cluster_stats.silhouette_score(Xd, labels)
+                sil_dn = cluster_stats.silhouette_score(Xd[torch.as_tensor(keep, device=dev)], labels[keep])
+                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(labels), sil))
+                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(int(keep.sum()), sil_dn))
+            rows.append([eps, len(core), n_clusters_, n_noise_, sil, sil_dn, self.k, self.min_sample])
+        df = pd.DataFrame(rows, columns=self.COLUMNS)
+        df.to_csv(eps_csv, index=False)
+        pd.DataFrame({'similarity': np.arange(self.k + 1), 'pairs': stats['similarity_hist']}).to_csv(hist_csv, index=False)
+        pd.DataFrame({'eps{}'.format(e): fit[0] for e, fit in zip(self.eps_values, fits)}).to_csv(labels_csv, index=False)
+        logger.info('Saved for {}!.'.format(eps_csv))
+        self.labels_, self.stats_ = {e: fit[0] for e, fit in zip(self.eps_values, fits)}, stats
         return df
 
 
@@ -714,6 +788,13 @@ class Cluster(object):
                     gm = Gmm(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gmm_covariance_type,
                              self.args.metric_sample)
                     results[metric] = gm.train(self.train_data, self.valid_data)
+                continue
+            if self.args.cluster_method == 'snn':
+                if dist.rank() == 0:            # one graph, on rank 0; the other ranks wait at main's barrier
+                    k = self.args.snn_k if self.args.snn_k is not None else self.feat_dim + 1
+                    eps_values = self.args.snn_eps or snn_default_eps(k)
+                    sn = Snn(k, eps_values, self.args.snn_min_samples if self.args.snn_min_samples is not None else k // 4, self.out_path)
+                    results[metric] = sn.train(self.train_data, self.valid_data)
                 continue
             if self.args.cluster_method != 'kmeans':
                 raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan and ward are on the accelerated path")

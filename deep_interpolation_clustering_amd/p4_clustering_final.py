@@ -11,11 +11,15 @@ provide here: it raises.  (p2's optics branch exists: optics.py.)
 ``hdbscan`` (no upstream counterpart; the dbscan branch without its eps): an HDBSCAN(min_cluster_size = --hdbscan_min_cluster_size, default feat_dim + 1,
 min_samples = feat_dim + 1) fit per cohort on the GPU (hdbscan.py), training clusters re-numbered by sbp, validation / test clusters mapped onto the nearest
 training centre, exactly as the dbscan branch does it; writes <cohort>_mcs-<min_cluster_size>.npy.
-``--transfer knn`` (dbscan and hdbscan; no upstream counterpart): only the training cohort is fitted and re-numbered by sbp; every validation / test
+``--transfer knn`` (dbscan, hdbscan and snn; no upstream counterpart): only the training cohort is fitted and re-numbered by sbp; every validation / test
 encounter takes the label most frequent among its --transfer_k (default feat_dim + 1) nearest training encounters, noise being a label like any other
 (knn.knn_transfer_labels: the vote of KNeighborsClassifier).  That works whatever the cohorts' own cluster counts would have been and labels a non-convex
 cluster by its members, not its centre.  Writes <cohort>_eps-<opt_eps>_knn.npy / <cohort>_mcs-<min_cluster_size>_knn.npy with ``cluster_id`` and
 ``cluster_vote``, the winning label's share of the votes (1 for the training cohort).  The default, ``--transfer centre``, is the behaviour above.
+``snn`` (no upstream counterpart; the dbscan branch with shared neighbours in place of the euclidean radius): an SNN(n_neighbors = --snn_k, default feat_dim + 1,
+eps = --snn_eps shared neighbours, default round(k / 2), min_samples = --snn_min_samples, default k // 4) fit per cohort on the GPU (snn.py), aligned and
+transferred exactly as the dbscan branch does it, --transfer knn included; writes <cohort>_snn-k<k>-eps<eps>-ms<min_samples>[_knn].npy.  The two defaults
+are starting points, not measured on the real latents.
 ``consensus`` (p4:241-287): reads the raw consensus labels of out_feat/raw_consensus_result/<cohort>_consensus.csv (column k<num_clusters>, 0- or 1-based),
 re-numbers the training clusters by sbp (generate_align_map) and applies that map to the training and the validation cohort (upstream leaves the test cohort
 out); writes <cohort>_<k>.npy.  Upstream's csv files were "generated outside"; a missing one is first computed here by consensus clustering of that cohort's
@@ -42,6 +46,7 @@ from .hdbscan import HDBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
 from .knn import knn_transfer_labels
+from .snn import SNN
 from .utils import logger, print_dict_byline
 from .ward import Ward
 
@@ -50,11 +55,18 @@ np.random.seed(123)        # p4_clustering_final.py:24
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
     p.add_argument('--hdbscan_min_cluster_size', type=int, default=None, help='(extra) min_cluster_size of --cluster_method hdbscan; default feat_dim + 1')
+    p.add_argument('--snn_k', type=int, default=None, help='(extra) neighbours per point of --cluster_method snn; default feat_dim + 1')
+    p.add_argument('--snn_eps', type=int, default=None,
+                   help='(extra) shared-neighbour threshold of --cluster_method snn, an integer in [1, k]; default round(k / 2) -- a starting point, not '
+                        "measured on the real latents: read it from p2's plot/snn_similarity_hist.csv")
+    p.add_argument('--snn_min_samples', type=int, default=None,
+                   help='(extra) strong links that make a core point of --cluster_method snn (0: Jarvis-Patrick); default k // 4 -- a starting point, not '
+                        'measured on the real latents')
     p.add_argument('--transfer', default='centre', choices=['centre', 'knn'],
                    help="(extra) how --cluster_method dbscan / hdbscan label the validation and test cohorts: 'centre' fits each cohort and maps its clusters onto "
                         "the nearest training centre (upstream); 'knn' fits the training cohort only and votes among the nearest training encounters")
@@ -126,26 +138,25 @@ class Cluster(object):
         label, vote = knn_transfer_labels(train_ref[0], np.asarray(train_ref[1]).astype(np.int64), feat, k)
         return label.astype(np.asarray(train_ref[1]).dtype), vote
 
-    def _dbscan(self, cohorts, overwrite):
-        opt_eps = self.args.opt_eps
-        logger.info('==> Generate the DBSCAN results with opt-eps: {}'.format(opt_eps))
+    def _density_branch(self, cohorts, overwrite, name, title, fit):
+        """The dbscan, hdbscan and snn branches: ``fit(feat) -> (raw labels, core points or None)`` per cohort, training clusters re-numbered by sbp,
+        validation / test clusters mapped onto the nearest training centre -- or, with --transfer knn, only the training cohort fitted and the others voted
+        (``_knn_labels``).  ``name``: the file name with the cohort left open; ``title``: the method's name in the log."""
         train_feat_centers = None
         knn = getattr(self.args, 'transfer', 'centre') == 'knn'
-        name = '{}_eps-{}_knn.npy' if knn else '{}_eps-{}.npy'
         train_ref = None
         for cohort, data in cohorts:
-            f = osp.join(self.out_path, name.format(cohort, opt_eps))
+            f = osp.join(self.out_path, name.format(cohort))
             if osp.exists(f) and not overwrite:
                 logger.info('Not Save for {}.'.format(f))
                 continue
             feat = data['hidden']
+            n_core = None
             if knn and cohort != 'training':
-                aligned_label, data['cluster_vote'] = self._knn_labels(osp.join(self.out_path, name.format('training', opt_eps)), train_ref, feat)
-                db = None
+                aligned_label, data['cluster_vote'] = self._knn_labels(osp.join(self.out_path, name.format('training')), train_ref, feat)
             else:
-                logger.info('NEW DBSCAN model for {}'.format(cohort))
-                db = DBSCAN(opt_eps, feat.shape[-1]).fit(feat)
-                raw_label = db.labels_
+                logger.info('NEW {} model for {}'.format(title, cohort))
+                raw_label, n_core = fit(feat)
                 if cohort == 'training':
                     _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
                 else:
@@ -155,8 +166,8 @@ class Cluster(object):
                     data['cluster_vote'] = np.ones(len(aligned_label), dtype=np.float32)
             data['cluster_id'] = aligned_label
             del data['ob'], data['padding_mask']
-            if db is not None:
-                logger.info('core_sample: {}'.format(len(db.core_sample_indices_)))
+            if n_core is not None:
+                logger.info('core_sample: {}'.format(n_core))
             n_clusters_ = len(set(aligned_label)) - (1 if -1 in aligned_label else 0)
             n_noise_ = int(np.sum(aligned_label == -1))
             keep = aligned_label != -1
@@ -173,49 +184,36 @@ class Cluster(object):
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
             np.save(f, data)
 
+    def _dbscan(self, cohorts, overwrite):
+        opt_eps = self.args.opt_eps
+        logger.info('==> Generate the DBSCAN results with opt-eps: {}'.format(opt_eps))
+        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
+
+        def fit(feat):
+            db = DBSCAN(opt_eps, feat.shape[-1]).fit(feat)
+            return db.labels_, len(db.core_sample_indices_)
+        self._density_branch(cohorts, overwrite, '{{}}_eps-{}{}.npy'.format(opt_eps, '_knn' if knn else ''), 'DBSCAN', fit)
+
     def _hdbscan(self, cohorts, overwrite):
         min_samples = self.feat_dim + 1
         mcs = self.args.hdbscan_min_cluster_size if self.args.hdbscan_min_cluster_size is not None else self.feat_dim + 1
         logger.info('==> Generate the HDBSCAN results with min_cluster_size: {}, min_samples: {}'.format(mcs, min_samples))
-        train_feat_centers = None
         knn = getattr(self.args, 'transfer', 'centre') == 'knn'
-        name = '{}_mcs-{}_knn.npy' if knn else '{}_mcs-{}.npy'
-        train_ref = None
-        for cohort, data in cohorts:
-            f = osp.join(self.out_path, name.format(cohort, mcs))
-            if osp.exists(f) and not overwrite:
-                logger.info('Not Save for {}.'.format(f))
-                continue
-            feat = data['hidden']
-            if knn and cohort != 'training':
-                aligned_label, data['cluster_vote'] = self._knn_labels(osp.join(self.out_path, name.format('training', mcs)), train_ref, feat)
-            else:
-                logger.info('NEW HDBSCAN model for {}'.format(cohort))
-                raw_label = HDBSCAN(min_cluster_size=mcs, min_samples=min_samples).fit(feat).labels_
-                if cohort == 'training':
-                    _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
-                else:
-                    aligned_label = self.align_labels_with_center(feat, raw_label, train_feat_centers)
-                if knn:
-                    train_ref = (feat, aligned_label)
-                    data['cluster_vote'] = np.ones(len(aligned_label), dtype=np.float32)
-            data['cluster_id'] = aligned_label
-            del data['ob'], data['padding_mask']
-            n_clusters_ = len(set(aligned_label)) - (1 if -1 in aligned_label else 0)
-            n_noise_ = int(np.sum(aligned_label == -1))
-            keep = aligned_label != -1
-            logger.info('Estimated number of clusters: %d' % n_clusters_)
-            logger.info('Estimated number of noise points: %d' % n_noise_)
-            if n_clusters_ == 0:
-                continue                      # (as the dbscan branch: nothing is written for this cohort)
-            elif n_clusters_ == 1:
-                logger.info('Skip the Silhouette Coefficient calculation.')
-            else:
-                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(aligned_label), cluster_stats.silhouette_score(feat, aligned_label)))
-                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(
-                    int(keep.sum()), cluster_stats.silhouette_score(feat[keep], aligned_label[keep])))
-            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
-            np.save(f, data)
+        self._density_branch(cohorts, overwrite, '{{}}_mcs-{}{}.npy'.format(mcs, '_knn' if knn else ''), 'HDBSCAN',
+                             lambda feat: (HDBSCAN(min_cluster_size=mcs, min_samples=min_samples).fit(feat).labels_, None))
+
+    def _snn(self, cohorts, overwrite):
+        """The dbscan branch with shared neighbours in place of the euclidean radius: SNN(--snn_k, --snn_eps, --snn_min_samples) per cohort."""
+        k = self.args.snn_k if self.args.snn_k is not None else self.feat_dim + 1
+        eps = self.args.snn_eps if self.args.snn_eps is not None else int(round(k * 0.5))
+        ms = self.args.snn_min_samples if self.args.snn_min_samples is not None else k // 4
+        logger.info('==> Generate the SNN results with k: {}, eps: {}, min_samples: {}'.format(k, eps, ms))
+        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
+
+        def fit(feat):
+            sn = SNN(k, eps, ms).fit(feat)
+            return sn.labels_, len(sn.core_sample_indices_)
+        self._density_branch(cohorts, overwrite, '{{}}_snn-k{}-eps{}-ms{}{}.npy'.format(k, eps, ms, '_knn' if knn else ''), 'SNN', fit)
 
     def _ward(self, cohorts, overwrite):
         """The kmeans branch with one Ward tree of the training latents in place of the k-means fits: the tree is cut at --num_clusters, generate_align_map
@@ -315,7 +313,7 @@ class Cluster(object):
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         transfer = getattr(self.args, 'transfer', 'centre')          # (an args object from before the flag: the default)
-        if transfer != 'centre' and self.args.cluster_method not in ('dbscan', 'hdbscan'):
+        if transfer != 'centre' and self.args.cluster_method not in ('dbscan', 'hdbscan', 'snn'):
             raise ValueError("--transfer {} applies to --cluster_method dbscan and hdbscan only: '{}' labels every cohort with its training model "
                              "already".format(transfer, self.args.cluster_method))
         for metric in self.args.restore_metric:
@@ -359,6 +357,8 @@ class Cluster(object):
                 self._consensus(overwrite)
             elif self.args.cluster_method == 'hdbscan':
                 self._hdbscan(cohorts, overwrite)
+            elif self.args.cluster_method == 'snn':
+                self._snn(cohorts, overwrite)
             elif self.args.cluster_method == 'ward':
                 self._ward(cohorts, overwrite)
             elif self.args.cluster_method == 'gmm':

@@ -646,6 +646,33 @@ size_t dic_knn_neighbors_workspace(int64_t N, int64_t M, int D, int64_t candidat
 int dic_knn_neighbors(const float* X, long ldx, int64_t N, const float* Q, long ldq, int64_t M, const float* centre, int D, int k, double* dist, int32_t* idx,
                       int64_t candidate_budget, int64_t* stats, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* Shared-nearest-neighbour clustering on the neighbour lists (csrc/dic_snn.hip; Jarvis & Patrick 1973; Ertoz, Steinbach & Kumar 2003); no upstream counterpart.
+ * THE DEFINITION, which snn.py, p2, p4 and the tests hold to.  k = n_neighbors, 2 <= k <= min(N, 1024).  L(i) = row i of the self join's idx (N, k) int32 from
+ * dic_knn_neighbors: the k index points with the smallest (d^2, index) keys, the point itself an ordinary neighbour (L(i) contains i unless k or more exact
+ * duplicates with smaller indices precede it; nothing below relies on it).
+ *   similarity  for column c, j = L(i)[c]:  sim[i, c] = |L(i) n L(j)|  if j != i and i is in L(j) (a MUTUAL pair), else 0.  Symmetric: sim of (i, j) read
+ *               from row i equals sim of (j, i) read from row j.
+ *   density     density[i] = #{c : sim[i, c] >= eps}, eps an integer, 1 <= eps <= k.
+ *   core        i is a core point iff density[i] >= min_samples, min_samples >= 0.  min_samples = 0 makes every point core: Jarvis-Patrick clustering, the
+ *               components of the mutual graph thresholded at eps, an isolated point a cluster of its own.
+ *   clusters    the connected components of the core points under the edges sim >= eps between two cores; cluster id = the rank of the component's smallest
+ *               core index (dbscan.py's numbering).
+ *   border      a non-core point with at least one edge sim >= eps to a core point takes the cluster of the core j with the largest sim; on equal sim the
+ *               smaller j.
+ *   noise       everything else: -1.
+ * All results are integers; two calls give the same values.  idx, sim, density, labels, border, changed: DEVICE, 4-B aligned.  N < 2^30.
+ *   dic_snn_similarity: sim (N, k) int32 OVERWRITTEN, every entry.  An entry of idx outside [0, N) is treated as absent from its list and is never used as a
+ *       row index (its sim is 0): garbage lists give garbage counts, never an out-of-range access.  One pass over the lists, N k^2 entries read.
+ *   dic_snn_components_pass: one label pass over the sparse graph, then a pointer-jump launch -- the protocol of dic_dbscan_components_pass.  density (N)
+ *       int32 as defined above (torch: (sim >= eps).sum(1)).  labels (N) int32, initialised by the caller to 0..N-1: every core point takes the smallest label
+ *       among itself and its strong core neighbours and hooks its root to it (atomicMin), then labels jump to their roots.  *changed (int32, zeroed by the
+ *       caller) is set to 1 when a label moved.  Repeat until a pass leaves *changed at 0; then labels[i] (core i) = the smallest core index of i's
+ *       component.  border (N) int32 OVERWRITTEN by every pass with the same values: for a border point the core j it belongs to under the rule above (its
+ *       cluster is that of labels[border[i]]), -1 for core and noise points. */
+int dic_snn_similarity(const int32_t* idx, int64_t N, int k, int32_t* sim, dic_stream_t stream);
+int dic_snn_components_pass(const int32_t* idx, const int32_t* sim, int64_t N, int k, int eps, const int32_t* density, int min_samples, int32_t* labels,
+                            int32_t* border, int32_t* changed, dic_stream_t stream);
+
 /* OPTICS' ordering without the distance matrix (csrc/dic_optics.hip): p2_clustering_optK.py:86-88,171-223 fits sklearn.cluster.OPTICS; this is its main loop
  * in the self-consistent form sklearn has with metric='precomputed' on the f64 difference-form distances d of the f32 points.  X, ldx, N, D as for
  * dic_knn_kth_distance (D <= 256, D % 4 == 0, N < 2^30, X and the workspace 16-B aligned).  core (N) f64, DEVICE, in: the core distances, already set to inf
