@@ -140,6 +140,10 @@ SIGNATURES = {
     'dic_knn_neighbors': (_i, [_p, C.c_long, C.c_int64, _p, C.c_long, C.c_int64, _p, _i, _i, _p, _p, C.c_int64, _p, _p, _sz, _p]),
     'dic_snn_similarity': (_i, [_p, C.c_int64, _i, _p, _p]),
     'dic_snn_components_pass': (_i, [_p, _p, C.c_int64, _i, _i, _p, _i, _p, _p, _p, _p]),
+    'dic_spectral_spmm': (_i, [_p, _p, _p, _p, C.c_int64, C.c_int64, _i, _p, _p, C.c_double, C.c_double, C.c_double, _p, _p]),
+    'dic_spectral_gram_workspace': (_sz, [C.c_int64, _i]),
+    'dic_spectral_gram': (_i, [_p, _p, C.c_int64, _i, _p, _p, _sz, _p]),
+    'dic_spectral_rotate': (_i, [_p, _p, C.c_int64, _i, _p, _p]),
     'dic_optics_workspace': (_sz, [C.c_int64, _i]),
     'dic_optics_order': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_double, _p, _p, _p, _p, _sz, _p]),
     'dic_hdbscan_workspace': (_sz, [C.c_int64, _i]),

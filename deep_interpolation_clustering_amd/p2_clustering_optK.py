@@ -52,6 +52,12 @@ eps of the dbscan branch flips from all noise to one cluster within a narrow ban
 min_samples -- goes to <metric>_snn_aligned/plot/snn_eps.csv, the list entries per similarity 0..k -- the curve eps is read from, as the k-distance graph is
 for DBSCAN -- to plot/snn_similarity_hist.csv (similarity, pairs) and the labels to plot/snn_labels.csv, one column eps<eps> per eps.  The defaults of
 --snn_eps and --snn_min_samples are starting points: nobody has measured them on the real latents.
+``--cluster_method spectral`` (no upstream counterpart): spectral clustering of the training latents on the GPU (spectral.py: the symmetrised --spectral_k
+neighbour graph, default 10 as in sklearn, and the largest eigenpairs of its normalised adjacency by Chebyshev-filtered subspace iteration).  ONE graph and ONE
+decomposition with k_max + 1 eigenpairs serve K = 2..k_max: the labels of K come from the first K eigenvectors by --spectral_assign kmeans | cluster_qr.  The
+eigenvalues and their gaps go to <metric>_spectral_aligned/plot/spectral_eigenvalues.csv (index, eigenvalue, eigengap: the gap to the next one, so the gap after
+k_max is there), the per-K table (k, eigengap, n_iter, converged, n_connected_components and the --internal_metrics on the latents) to plot/spectral_k.csv and
+the 0-based labels to plot/spectral_labels.csv, one column k<K> per K.  The default --spectral_k is a starting point: DESIGN.md records what it gives.
 
 The seaborn plots of the upstream script are not provided.
 """
@@ -76,6 +82,8 @@ from .kmeans import KMeans, seed_draw_count
 from .knn import k_distance_graph
 from .optics import OPTICS
 from .snn import snn_sweep
+from ._native import MAX_CLUSTERS
+from .spectral import spectral_sweep
 from .utils import logger, print_dict_byline
 from .ward import Ward as WardLinkage
 
@@ -84,7 +92,7 @@ np.random.seed(123)        # p2_clustering_optK.py:23
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral'])
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -102,6 +110,8 @@ def get_arguments(argv=None):
     p.add_argument('--snn_eps', type=int, nargs='+', default=None,
                    help='(extra) shared-neighbour thresholds of --cluster_method snn, integers in [1, k]; default round(k t / 10) for t = 2..8 -- a starting '
                         'point, not measured on the real latents: read eps from plot/snn_similarity_hist.csv')
+    p.add_argument('--spectral_k', type=int, default=10, help="(extra) neighbours per point of --cluster_method spectral; default 10, sklearn's")
+    p.add_argument('--spectral_assign', default='kmeans', choices=['kmeans', 'cluster_qr'], help='(extra) how --cluster_method spectral labels the embedding')
     p.add_argument('--snn_min_samples', type=int, default=None,
                    help='(extra) strong links that make a core point of --cluster_method snn (0: Jarvis-Patrick); default k // 4 -- a starting point, not '
                         'measured on the real latents')
@@ -688,6 +698,67 @@ class Gmm(object):
         return df
 
 
+class Spectral(object):
+    """One spectral decomposition of the training latents (``spectral.spectral_sweep``: ``k`` neighbours, k_max + 1 eigenpairs) labelled for K = 2..``k_max``
+    from the first K eigenvectors.  Per K: the eigengap theta_K - theta_(K+1), the solver's iterations and whether it converged, the number of connected
+    components and the ``internal_metrics`` of the labels on the latents as ``KM`` computes them -- one shared pair pass per K, ``metric_sample`` honoured.
+    Writes plot/spectral_eigenvalues.csv (index 1..k_max + 1, eigenvalue, eigengap: the gap to the next eigenvalue, NaN for the last), plot/spectral_k.csv and
+    plot/spectral_labels.csv (columns k2..k<k_max>, 0-based) and returns the per-K table.  Existing files are left alone unless ``overwrite`` is set; the
+    table on disk is returned then.  ``fit_`` keeps the fitted ``spectral.SpectralClustering`` of the last run that computed one."""
+    FILES = ('spectral_eigenvalues.csv', 'spectral_k.csv', 'spectral_labels.csv')
+
+    def __init__(self, k_max, out_path, internal_metrics, k=10, assign_labels='kmeans', metric_sample=0):
+        if not 2 <= k_max <= MAX_CLUSTERS - 1:
+            raise ValueError('--cluster_method spectral: --k_max must lie in [2, {}] (k_max + 1 eigenpairs are computed, for the gap after the last K, and '
+                             '{} is the compiled limit), got {}'.format(MAX_CLUSTERS - 1, MAX_CLUSTERS, k_max))
+        self.ks = list(range(2, k_max + 1))
+        self.k, self.assign_labels = k, assign_labels
+        self.metric_sample = metric_sample
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.internal_metrics_names = list(internal_metrics)
+        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
+        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self.fit_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fit_ = None
+        eig_csv, k_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (eig_csv, k_csv, labels_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(k_csv))
+            return pd.read_csv(k_csv, float_precision='round_trip')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        fit = spectral_sweep(Xd, self.ks, n_neighbors=self.k, assign_labels=self.assign_labels, random_state=0, n_components=self.ks[-1] + 1,
+                             return_fit=True)
+        theta = fit.eigenvalues_
+        gaps = np.append(theta[:-1] - theta[1:], np.nan)
+        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
+        rows = []
+        for k in self.ks:
+            logger.info('Running K: {}'.format(k))
+            labels = np.unique(fit.labels_by_k_[k], return_inverse=True)[1].astype(np.int64)          # (an empty cluster is skipped by the indices)
+            if labels.max() < 1:          # (the indices need two clusters)
+                vals = [float('nan')] * len(self.internal_metrics)
+            elif self.metric_sample and self.metric_sample < len(labels):
+                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
+                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
+            else:
+                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
+                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
+            logger.info('k: {}, eigengap: {:.6f}, n_iter: {}, components: {} '.format(k, gaps[k - 1], fit.n_iter_, fit.n_connected_components_)
+                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+            rows.append([k, gaps[k - 1], fit.n_iter_, int(fit.converged_), fit.n_connected_components_] + vals)
+        df = pd.DataFrame(rows, columns=['k', 'eigengap', 'n_iter', 'converged', 'n_connected_components'] + self.internal_metrics_names)
+        pd.DataFrame({'index': np.arange(1, len(theta) + 1), 'eigenvalue': theta, 'eigengap': gaps}).to_csv(eig_csv, index=False, float_format='%.17g')
+        df.to_csv(k_csv, index=False, float_format='%.17g')
+        pd.DataFrame({'k{}'.format(k): fit.labels_by_k_[k] for k in self.ks}).to_csv(labels_csv, index=False)
+        logger.info('Saved for {}!.'.format(k_csv))
+        self.fit_ = fit
+        return df
+
+
 class Consensus(object):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
@@ -796,8 +867,14 @@ class Cluster(object):
                     sn = Snn(k, eps_values, self.args.snn_min_samples if self.args.snn_min_samples is not None else k // 4, self.out_path)
                     results[metric] = sn.train(self.train_data, self.valid_data)
                 continue
+            if self.args.cluster_method == 'spectral':
+                if dist.rank() == 0:            # one decomposition, on rank 0; the other ranks wait at main's barrier
+                    sp = Spectral(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.spectral_k, self.args.spectral_assign,
+                                  self.args.metric_sample)
+                    results[metric] = sp.train(self.train_data, self.valid_data)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan and ward are on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan, ward, gmm, snn and spectral are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

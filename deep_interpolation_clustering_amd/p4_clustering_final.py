@@ -11,7 +11,7 @@ provide here: it raises.  (p2's optics branch exists: optics.py.)
 ``hdbscan`` (no upstream counterpart; the dbscan branch without its eps): an HDBSCAN(min_cluster_size = --hdbscan_min_cluster_size, default feat_dim + 1,
 min_samples = feat_dim + 1) fit per cohort on the GPU (hdbscan.py), training clusters re-numbered by sbp, validation / test clusters mapped onto the nearest
 training centre, exactly as the dbscan branch does it; writes <cohort>_mcs-<min_cluster_size>.npy.
-``--transfer knn`` (dbscan, hdbscan and snn; no upstream counterpart): only the training cohort is fitted and re-numbered by sbp; every validation / test
+``--transfer knn`` (dbscan, hdbscan, snn and spectral; no upstream counterpart): only the training cohort is fitted and re-numbered by sbp; every validation / test
 encounter takes the label most frequent among its --transfer_k (default feat_dim + 1) nearest training encounters, noise being a label like any other
 (knn.knn_transfer_labels: the vote of KNeighborsClassifier).  That works whatever the cohorts' own cluster counts would have been and labels a non-convex
 cluster by its members, not its centre.  Writes <cohort>_eps-<opt_eps>_knn.npy / <cohort>_mcs-<min_cluster_size>_knn.npy with ``cluster_id`` and
@@ -20,6 +20,9 @@ cluster by its members, not its centre.  Writes <cohort>_eps-<opt_eps>_knn.npy /
 eps = --snn_eps shared neighbours, default round(k / 2), min_samples = --snn_min_samples, default k // 4) fit per cohort on the GPU (snn.py), aligned and
 transferred exactly as the dbscan branch does it, --transfer knn included; writes <cohort>_snn-k<k>-eps<eps>-ms<min_samples>[_knn].npy.  The two defaults
 are starting points, not measured on the real latents.
+``spectral`` (no upstream counterpart; a partition into exactly --num_clusters groups that need not be convex): a SpectralClustering(--num_clusters,
+n_neighbors = --spectral_k, default 10, assign_labels = --spectral_assign) fit per cohort on the GPU (spectral.py), aligned and transferred exactly as the
+dbscan branch does it, --transfer knn included (the method has no predict of its own); writes <cohort>_spectral-k<k>-K<K>[_knn].npy.
 ``consensus`` (p4:241-287): reads the raw consensus labels of out_feat/raw_consensus_result/<cohort>_consensus.csv (column k<num_clusters>, 0- or 1-based),
 re-numbers the training clusters by sbp (generate_align_map) and applies that map to the training and the validation cohort (upstream leaves the test cohort
 out); writes <cohort>_<k>.npy.  Upstream's csv files were "generated outside"; a missing one is first computed here by consensus clustering of that cohort's
@@ -47,6 +50,7 @@ from .info import COHORTS
 from .kmeans import KMeans
 from .knn import knn_transfer_labels
 from .snn import SNN
+from .spectral import SpectralClustering
 from .utils import logger, print_dict_byline
 from .ward import Ward
 
@@ -55,7 +59,7 @@ np.random.seed(123)        # p4_clustering_final.py:24
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
@@ -67,8 +71,10 @@ def get_arguments(argv=None):
     p.add_argument('--snn_min_samples', type=int, default=None,
                    help='(extra) strong links that make a core point of --cluster_method snn (0: Jarvis-Patrick); default k // 4 -- a starting point, not '
                         'measured on the real latents')
+    p.add_argument('--spectral_k', type=int, default=10, help="(extra) neighbours per point of --cluster_method spectral; default 10, sklearn's")
+    p.add_argument('--spectral_assign', default='kmeans', choices=['kmeans', 'cluster_qr'], help='(extra) how --cluster_method spectral labels the embedding')
     p.add_argument('--transfer', default='centre', choices=['centre', 'knn'],
-                   help="(extra) how --cluster_method dbscan / hdbscan label the validation and test cohorts: 'centre' fits each cohort and maps its clusters onto "
+                   help="(extra) how --cluster_method dbscan / hdbscan / snn / spectral label the validation and test cohorts: 'centre' fits each cohort and maps its clusters onto "
                         "the nearest training centre (upstream); 'knn' fits the training cohort only and votes among the nearest training encounters")
     p.add_argument('--transfer_k', type=int, default=None, help='(extra) neighbours of --transfer knn; default feat_dim + 1')
     p.add_argument('--dl_cluster_label_type', default='pred', choices=['label', 'pred'])
@@ -215,6 +221,14 @@ class Cluster(object):
             return sn.labels_, len(sn.core_sample_indices_)
         self._density_branch(cohorts, overwrite, '{{}}_snn-k{}-eps{}-ms{}{}.npy'.format(k, eps, ms, '_knn' if knn else ''), 'SNN', fit)
 
+    def _spectral(self, cohorts, overwrite):
+        """The dbscan branch with a spectral partition into --num_clusters groups in place of the density clusters (no noise label, no core points)."""
+        K, k, assign = self.args.num_clusters, self.args.spectral_k, self.args.spectral_assign
+        logger.info('==> Generate the spectral clustering results with opt-k: {}, neighbours: {}, assign_labels: {}'.format(K, k, assign))
+        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
+        self._density_branch(cohorts, overwrite, '{{}}_spectral-k{}-K{}{}.npy'.format(k, K, '_knn' if knn else ''), 'spectral clustering',
+                             lambda feat: (SpectralClustering(K, n_neighbors=k, assign_labels=assign).fit(feat).labels_, None))
+
     def _ward(self, cohorts, overwrite):
         """The kmeans branch with one Ward tree of the training latents in place of the k-means fits: the tree is cut at --num_clusters, generate_align_map
         orders the clusters by sbp and the centres (the means of the members) are re-ordered with the map.  The training cohort keeps its tree labels,
@@ -313,8 +327,8 @@ class Cluster(object):
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         transfer = getattr(self.args, 'transfer', 'centre')          # (an args object from before the flag: the default)
-        if transfer != 'centre' and self.args.cluster_method not in ('dbscan', 'hdbscan', 'snn'):
-            raise ValueError("--transfer {} applies to --cluster_method dbscan and hdbscan only: '{}' labels every cohort with its training model "
+        if transfer != 'centre' and self.args.cluster_method not in ('dbscan', 'hdbscan', 'snn', 'spectral'):
+            raise ValueError("--transfer {} applies to --cluster_method dbscan and hdbscan only (and to snn and spectral, which follow their branch): '{}' labels every cohort with its training model "
                              "already".format(transfer, self.args.cluster_method))
         for metric in self.args.restore_metric:
             self.feat_path = osp.join(self.exp_path, 'out_feat', metric)
@@ -359,6 +373,8 @@ class Cluster(object):
                 self._hdbscan(cohorts, overwrite)
             elif self.args.cluster_method == 'snn':
                 self._snn(cohorts, overwrite)
+            elif self.args.cluster_method == 'spectral':
+                self._spectral(cohorts, overwrite)
             elif self.args.cluster_method == 'ward':
                 self._ward(cohorts, overwrite)
             elif self.args.cluster_method == 'gmm':

@@ -784,6 +784,33 @@ int dic_gmm_mstep_labels(const float* X, long ldx, int64_t N, int D, int D0, int
                          const int32_t* labels, const double* resp, double* weights, double* means, double* variances, void* workspace,
                          size_t workspace_bytes, dic_stream_t stream);
 
+/* Spectral clustering on the symmetrised k-neighbour graph (csrc/dic_spectral.hip, spectral.py): sklearn 1.7.2's
+ * SpectralClustering(affinity='nearest_neighbors'), stated here once.
+ *   L(i): the list of the k nearest neighbours of point i from dic_knn_neighbors, self join (the point itself its first entry), 2 <= k.  A: the 0/1 matrix of
+ *   the lists.  W = 0.5 (A + A^T), entries 0.5 or 1, its diagonal dropped before the degrees are taken (scipy's laplacian).  deg_i = sum_j W_ij > 0 (k >= 2:
+ *   every point has an off-diagonal neighbour), dd_i = sqrt(deg_i).  M = D^-1/2 W D^-1/2 has its spectrum in [-1, 1]; sklearn's Laplacian is I - M.  Wanted:
+ *   the m largest eigenpairs (theta_1 >= .. >= theta_m, V) of M.  Embedding = V / dd row-wise, then every eigenvector's entry of largest magnitude made
+ *   positive, the first one on equal magnitude (_deterministic_vector_sign_flip).  Labels: k-means (n_init = 10) or sklearn's cluster_qr on the first K
+ *   columns of the embedding.  The multiplicity of the eigenvalue 1 is the number of connected components of the graph.
+ * The graph is a CSR without its diagonal: indptr (N + 1) int64, indices (nnz) int32 ascending within a row, weight (nnz) one byte per entry, 1 = 0.5 and
+ * 2 = 1.0 (the kernel takes 0.5 * weight), dd (N) f64; all on the DEVICE and only read.  M is never stored: M_ij = (0.5 weight) / (dd_i * dd_j), one
+ * multiplication and one division in f64 -- symmetric in i and j bit for bit.  Rows may be of any length up to N (hub points).  An entry of indices outside
+ * [0, N) is absent from its row, and indptr is clamped to [0, nnz]: nothing outside the arrays is read.
+ * Blocks are (N, b) f64 row-major on the DEVICE, 1 <= b <= 64, 1 <= N < 2^30, 8-B aligned.  Every kernel is f64 throughout, has no floating-point atomics and
+ * no workgroup that waits for another; every result has the same bits from call to call, and the order of every sum is a function of the operands' shapes
+ * (N, b, the row's entries) alone, not of the device or the grid.  Nothing synchronises `stream`.
+ *   dic_spectral_spmm: Y = alpha (M X) + beta X + gamma Z, the fused step of a three-term recurrence (Z NULL: no third term).  Y must not be X; Y may be Z.
+ *       (M X)[i, c]: with g = the power of two >= b and e = 64 / g, the entries of row i at positions s, s + e, s + 2 e, .. are added in ascending order, each
+ *       by one fma into the running sum, for every s < e; the e sums are then added in the xor tree s ^ 1, s ^ 2, ...
+ *   dic_spectral_gram: G (b, b) row-major OVERWRITTEN = A^T B.  Every workgroup sums 128 consecutive rows in ascending order (fma); the partials
+ *       (dic_spectral_gram_workspace(N, b) bytes, 8-B aligned) are added in block order by a second kernel.
+ *   dic_spectral_rotate: Y = X C, C (b, b) row-major on the DEVICE, the sum over p ascending (fma).  Y must not be X. */
+int dic_spectral_spmm(const int64_t* indptr, const int32_t* indices, const unsigned char* weight, const double* dd, int64_t N, int64_t nnz, int b,
+                      const double* X, const double* Z, double alpha, double beta, double gamma, double* Y, dic_stream_t stream);
+size_t dic_spectral_gram_workspace(int64_t N, int b);
+int dic_spectral_gram(const double* A, const double* B, int64_t N, int b, double* G, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_spectral_rotate(const double* X, const double* C, int64_t N, int b, double* Y, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
