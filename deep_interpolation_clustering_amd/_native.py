@@ -144,6 +144,11 @@ SIGNATURES = {
     'dic_spectral_gram_workspace': (_sz, [C.c_int64, _i]),
     'dic_spectral_gram': (_i, [_p, _p, C.c_int64, _i, _p, _p, _sz, _p]),
     'dic_spectral_rotate': (_i, [_p, _p, C.c_int64, _i, _p, _p]),
+    'dic_meanshift_workspace': (_sz, [C.c_int64, C.c_int64]),
+    'dic_meanshift_prepare': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, _p, _sz, _p]),
+    'dic_meanshift_members': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, C.c_int64, C.c_int64, C.c_double, _p, _p, C.c_int64, _p, _p, _sz, _p]),
+    'dic_meanshift_shift': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, C.c_int64, _p, C.c_double, _i, _p, _p, _p, _p, _p]),
+    'dic_meanshift_nearest': (_i, [_p, C.c_long, _p, C.c_int64, _i, _p, _i, _p, _p, _p]),
     'dic_optics_workspace': (_sz, [C.c_int64, _i]),
     'dic_optics_order': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_double, _p, _p, _p, _p, _sz, _p]),
     'dic_hdbscan_workspace': (_sz, [C.c_int64, _i]),

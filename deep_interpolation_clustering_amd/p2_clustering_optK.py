@@ -59,6 +59,13 @@ eigenvalues and their gaps go to <metric>_spectral_aligned/plot/spectral_eigenva
 k_max is there), the per-K table (k, eigengap, n_iter, converged, n_connected_components and the --internal_metrics on the latents) to plot/spectral_k.csv and
 the 0-based labels to plot/spectral_labels.csv, one column k<K> per K.  The default --spectral_k is a starting point: DESIGN.md records what it gives.
 
+``--cluster_method meanshift`` (no upstream counterpart): mean shift with the flat kernel on the training latents on the GPU (meanshift.py: every point a seed
+unless --meanshift_bin_seeding, all seeds advancing together, no N x N structure) -- the one family here that both picks the number of clusters itself and
+gives centres to carry to the other cohorts.  One fit per bandwidth: --meanshift_bandwidth, or estimate_bandwidth at every --meanshift_quantile (default 0.1
+0.2 0.3).  The per-bandwidth table (quantile, bandwidth, n_clusters, n_orphans, largest, smallest, n_iter, valid_distortion: the validation cohort's mean
+distance to its nearest centre, and the --internal_metrics) goes to <metric>_meanshift_aligned/plot/meanshift_bandwidth.csv, the labels to
+plot/meanshift_labels.csv, one column bw<index> per bandwidth, and the centres to plot/meanshift_centers.csv (bandwidth, cluster, the coordinates), %.17g.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -79,6 +86,7 @@ from .hdbscan import hdbscan_sizes
 from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
 from .kmeans import KMeans, seed_draw_count
+from .meanshift import estimate_bandwidth, mean_shift_sweep
 from .knn import k_distance_graph
 from .optics import OPTICS
 from .snn import snn_sweep
@@ -92,7 +100,7 @@ np.random.seed(123)        # p2_clustering_optK.py:23
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift'])
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -115,6 +123,12 @@ def get_arguments(argv=None):
     p.add_argument('--snn_min_samples', type=int, default=None,
                    help='(extra) strong links that make a core point of --cluster_method snn (0: Jarvis-Patrick); default k // 4 -- a starting point, not '
                         'measured on the real latents')
+    p.add_argument('--meanshift_quantile', type=float, nargs='+', default=[0.1, 0.2, 0.3],
+                   help='(extra) quantiles of --cluster_method meanshift: one fit per bandwidth estimate_bandwidth(training latents, quantile)')
+    p.add_argument('--meanshift_bandwidth', type=float, nargs='+', default=None, help='(extra) bandwidths of --cluster_method meanshift; overrides the quantiles')
+    p.add_argument('--meanshift_bin_seeding', action='store_true', help="(extra) seed --cluster_method meanshift from sklearn's bins, not from every point")
+    p.add_argument('--meanshift_cluster_all', type=int, default=1, choices=[1, 0],
+                   help='(extra) 0: a point farther than the bandwidth from its nearest centre is an orphan (-1)')
     p.add_argument('--metric_sample', type=int, default=0, help='(extra) subsample size for the O(N^2) validity indices; 0 = all')
     return p.parse_args(argv)
 
@@ -698,6 +712,78 @@ class Gmm(object):
         return df
 
 
+class Meanshift(object):
+    """Mean shift of the training latents (``meanshift.mean_shift_sweep``), one fit per bandwidth: the given ``bandwidths``, or ``estimate_bandwidth`` of the
+    training latents at every quantile of ``quantiles``.  Per bandwidth: the clusters found, the orphans (``cluster_all`` off), the largest and the smallest
+    cluster, the iterations, the validation cohort's mean distance to its nearest centre (``predict``) and the ``internal_metrics`` of the labels as ``KM``
+    computes them (orphans left out) -- one shared pair pass, ``metric_sample`` honoured -- logged per fit.  Writes plot/meanshift_bandwidth.csv,
+    plot/meanshift_labels.csv (columns bw0, bw1, .. in the table's order) and plot/meanshift_centers.csv (bandwidth, cluster, x0, x1, ..), all %.17g, and
+    returns the table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.  ``fits_`` keeps the fitted models
+    [``meanshift.MeanShift``] of the last run that computed them, in the table's order."""
+    FILES = ('meanshift_bandwidth.csv', 'meanshift_labels.csv', 'meanshift_centers.csv')
+    COLUMNS = ['quantile', 'bandwidth', 'n_clusters', 'n_orphans', 'largest', 'smallest', 'n_iter', 'valid_distortion']
+
+    def __init__(self, out_path, internal_metrics, quantiles=(0.1, 0.2, 0.3), bandwidths=None, bin_seeding=False, cluster_all=True, metric_sample=0):
+        self.quantiles, self.bandwidths = list(quantiles), None if bandwidths is None else [float(b) for b in bandwidths]
+        self.bin_seeding, self.cluster_all = bool(bin_seeding), bool(cluster_all)
+        self.metric_sample = metric_sample
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.internal_metrics_names = list(internal_metrics)
+        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
+        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self.fits_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fits_ = None
+        bw_csv, labels_csv, centers_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (bw_csv, labels_csv, centers_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(bw_csv))
+            return pd.read_csv(bw_csv, float_precision='round_trip')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        Vd = torch.as_tensor(valid_data['hidden'], dtype=torch.float32, device=dev)
+        if self.bandwidths is not None:
+            plan = [(float('nan'), b) for b in self.bandwidths]
+        else:
+            plan = [(q, estimate_bandwidth(Xd, q)) for q in self.quantiles]
+        by_bw = mean_shift_sweep(Xd, sorted(set(b for _, b in plan)), bin_seeding=self.bin_seeding, cluster_all=self.cluster_all)
+        fits = [by_bw[b] for _, b in plan]
+        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
+        rows = []
+        for (q, b), fit in zip(plan, fits):
+            logger.info('Running bandwidth: {:.6g} (quantile {})'.format(b, q))
+            keep = fit.labels_ >= 0
+            sizes = np.bincount(fit.labels_[keep], minlength=len(fit.cluster_centers_))
+            cv = fit.cluster_centers_[fit.predict(Vd)]
+            valid_d = float(np.sqrt(((np.asarray(valid_data['hidden'], dtype=np.float64) - cv) ** 2).sum(axis=1)).mean())
+            labels = np.unique(fit.labels_[keep], return_inverse=True)[1].astype(np.int64)
+            Xk = Xd if keep.all() else Xd[torch.as_tensor(keep, device=dev)]
+            if labels.size == 0 or labels.max() < 1:          # (the indices need two clusters)
+                vals = [float('nan')] * len(self.internal_metrics)
+            elif self.metric_sample and self.metric_sample < len(labels):
+                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
+                vals = [m(Xk[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
+            else:
+                stats = cluster_stats.pair_stats(Xk, labels, need_min=need_minmax, need_max=need_minmax)
+                vals = [m(Xk, labels, stats=stats) for m in self.internal_metrics]
+            row = [q, b, len(fit.cluster_centers_), int((~keep).sum()), int(sizes.max()), int(sizes.min()), fit.n_iter_, valid_d]
+            logger.info('bandwidth: {:.6g}, clusters: {}, orphans: {}, largest: {}, smallest: {}, n_iter: {}, valid: {:.4f} '.format(*row[1:])
+                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+            rows.append(row + vals)
+        df = pd.DataFrame(rows, columns=self.COLUMNS + self.internal_metrics_names)
+        df.to_csv(bw_csv, index=False, float_format='%.17g')
+        pd.DataFrame({'bw{}'.format(i): fit.labels_ for i, fit in enumerate(fits)}).to_csv(labels_csv, index=False)
+        width = fits[0].cluster_centers_.shape[1]
+        cen = [np.column_stack([np.full(len(f.cluster_centers_), b), np.arange(len(f.cluster_centers_)), f.cluster_centers_]) for (_, b), f in zip(plan, fits)]
+        pd.DataFrame(np.concatenate(cen), columns=['bandwidth', 'cluster'] + ['x{}'.format(c) for c in range(width)]).astype({'cluster': np.int64}).to_csv(
+            centers_csv, index=False, float_format='%.17g')
+        logger.info('Saved for {}!.'.format(bw_csv))
+        self.fits_ = fits
+        return df
+
+
 class Spectral(object):
     """One spectral decomposition of the training latents (``spectral.spectral_sweep``: ``k`` neighbours, k_max + 1 eigenpairs) labelled for K = 2..``k_max``
     from the first K eigenvectors.  Per K: the eigengap theta_K - theta_(K+1), the solver's iterations and whether it converged, the number of connected
@@ -873,8 +959,14 @@ class Cluster(object):
                                   self.args.metric_sample)
                     results[metric] = sp.train(self.train_data, self.valid_data)
                 continue
+            if self.args.cluster_method == 'meanshift':
+                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
+                    ms = Meanshift(self.out_path, self.args.internal_metrics, self.args.meanshift_quantile, self.args.meanshift_bandwidth,
+                                   self.args.meanshift_bin_seeding, bool(self.args.meanshift_cluster_all), self.args.metric_sample)
+                    results[metric] = ms.train(self.train_data, self.valid_data)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan, ward, gmm, snn and spectral are on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan, ward, gmm, snn, spectral and meanshift are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

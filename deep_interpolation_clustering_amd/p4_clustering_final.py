@@ -33,6 +33,10 @@ nearest training centre; writes <cohort>_<k>.npy.
 ``gmm`` (no upstream counterpart; the kmeans branch with a mixture in place of the centres): a Gaussian mixture of --num_clusters diagonal components fitted
 to the training latents on the GPU (gmm.py), the components re-numbered by sbp -- weights, means and covariances permuted with the map -- and every cohort
 labelled by ``predict`` of that one model; writes <cohort>_<k>.npy with ``cluster_id`` and ``cluster_prob``, the (N, K) f32 responsibilities.
+``meanshift`` (no upstream counterpart; the kmeans branch with the modes of the latent density in place of the centres, their number found by the fit): one
+mean shift fit of the training latents on the GPU (meanshift.py) at --meanshift_bandwidth, or at estimate_bandwidth(training latents,
+--meanshift_quantile); the centres re-numbered by sbp and every cohort labelled by ``predict``, the nearest centre -- with --meanshift_cluster_all 0 an
+encounter farther than the bandwidth from it is an orphan, -1; writes <cohort>_meanshift-bw<bandwidth, %.6g>.npy.
 """
 import argparse
 import copy
@@ -48,6 +52,7 @@ from .gmm import GaussianMixture
 from .hdbscan import HDBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
+from .meanshift import MeanShift, estimate_bandwidth
 from .knn import knn_transfer_labels
 from .snn import SNN
 from .spectral import SpectralClustering
@@ -59,7 +64,7 @@ np.random.seed(123)        # p4_clustering_final.py:24
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
@@ -73,6 +78,12 @@ def get_arguments(argv=None):
                         'measured on the real latents')
     p.add_argument('--spectral_k', type=int, default=10, help="(extra) neighbours per point of --cluster_method spectral; default 10, sklearn's")
     p.add_argument('--spectral_assign', default='kmeans', choices=['kmeans', 'cluster_qr'], help='(extra) how --cluster_method spectral labels the embedding')
+    p.add_argument('--meanshift_bandwidth', type=float, default=None, help='(extra) bandwidth of --cluster_method meanshift')
+    p.add_argument('--meanshift_quantile', type=float, default=None,
+                   help='(extra) without --meanshift_bandwidth: estimate_bandwidth(training latents, quantile); default 0.3, sklearn\'s')
+    p.add_argument('--meanshift_bin_seeding', action='store_true', help="(extra) seed --cluster_method meanshift from sklearn's bins, not from every point")
+    p.add_argument('--meanshift_cluster_all', type=int, default=1, choices=[1, 0],
+                   help='(extra) 0: an encounter farther than the bandwidth from its nearest centre is an orphan (-1), in every cohort')
     p.add_argument('--transfer', default='centre', choices=['centre', 'knn'],
                    help="(extra) how --cluster_method dbscan / hdbscan / snn / spectral label the validation and test cohorts: 'centre' fits each cohort and maps its clusters onto "
                         "the nearest training centre (upstream); 'knn' fits the training cohort only and votes among the nearest training encounters")
@@ -279,6 +290,38 @@ class Cluster(object):
             np.save(f, data)
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
 
+    def _meanshift(self, cohorts, overwrite):
+        """The kmeans branch with mean shift in place of k-means: one fit of the training cohort at the given or the estimated bandwidth finds the centres and
+        their number, generate_align_map orders them by sbp and the centres are permuted with the map.  Every cohort, training included, is labelled by
+        ``predict`` of that model (the training cohort's ``labels_`` are exactly that), with the orphan rule when --meanshift_cluster_all is 0."""
+        h = self.args.meanshift_bandwidth
+        if h is None:
+            q = self.args.meanshift_quantile if self.args.meanshift_quantile is not None else 0.3
+            h = estimate_bandwidth(self.train_data['hidden'], q)
+        cluster_all = bool(self.args.meanshift_cluster_all)
+        logger.info('==> Generate the mean shift results with bandwidth: {:.6g}, cluster_all: {}'.format(h, cluster_all))
+        model = MeanShift(bandwidth=h, bin_seeding=self.args.meanshift_bin_seeding, cluster_all=cluster_all).fit(self.train_data['hidden'])
+        k = len(model.cluster_centers_)
+        raw = np.array(model.labels_)
+        if set(raw.tolist()) - {-1} != set(range(k)):
+            raise ValueError('mean shift left {} of its {} centres without a training encounter: choose another bandwidth'.format(
+                k - len(set(raw.tolist()) - {-1}), k))
+        logger.info('Estimated number of clusters: {}, orphans: {}'.format(k, int(np.sum(raw == -1))))
+        align_map, _, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
+        order = np.empty(k, dtype=np.int64)
+        for old, new in align_map.items():
+            order[new] = old
+        model.reorder(order)
+        for cohort, data in cohorts:
+            f = osp.join(self.out_path, '{}_meanshift-bw{:.6g}.npy'.format(cohort, h))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            data['cluster_id'] = model.predict(data['hidden'], orphans=not cluster_all)
+            del data['ob'], data['padding_mask']
+            np.save(f, data)
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+
     def _raw_consensus(self, cohort, data):
         """The raw consensus labels of a cohort for k = num_clusters, 0-based as generate_align_map wants them (p4:247-253): column k<num_clusters> of
         raw_consensus_result/<cohort>_consensus.csv, computed and written first where the file is missing."""
@@ -379,6 +422,8 @@ class Cluster(object):
                 self._ward(cohorts, overwrite)
             elif self.args.cluster_method == 'gmm':
                 self._gmm(cohorts, overwrite)
+            elif self.args.cluster_method == 'meanshift':
+                self._meanshift(cohorts, overwrite)
             else:
                 raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus', 'hdbscan' and 'ward' are on the accelerated path: upstream's 'optics' branch of p4 is an "
                                           "empty `pass` (p2 has the OPTICS fit)")

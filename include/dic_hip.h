@@ -811,6 +811,46 @@ size_t dic_spectral_gram_workspace(int64_t N, int b);
 int dic_spectral_gram(const double* A, const double* B, int64_t N, int b, double* G, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 int dic_spectral_rotate(const double* X, const double* C, int64_t N, int b, double* Y, dic_stream_t stream);
 
+/* Mean shift with the flat kernel (csrc/dic_meanshift.hip, meanshift.py): sklearn 1.7.2's cluster/_mean_shift.py written as f64 arithmetic, stated here once.
+ *   Inputs: X (N, D) f32 points; x'_j = (double)x_j - c, c (D) f64 the column means.  A seed s is f64.  Bandwidth h > 0, t = h * h in f64.
+ *   Members: m(s) = { j : d2(s, j) <= t }.  d2 is the f64 difference form in the lane order of csrc/dic_exactd2.h: lane l holds coordinates 4 l .. 4 l + 3,
+ *       an fma chain over its four terms (s_k - (double)x_jk)^2 in coordinate order, then wave_sum's xor tree; the seed coordinate is f64 and the point
+ *       coordinate is promoted exactly.  The comparison is <=: a point at exactly h is a member.
+ *   One shift: |m(s)| = 0: the seed is finished with count 0 (and dropped later).  Otherwise s_new = c + (sum_{j in m(s)} x'_j) / |m(s)|,
+ *       moved = ||s_new - s||_2, s = s_new; the seed is finished if moved <= 1e-3 h or if it has already completed max_iter iterations, otherwise its
+ *       iteration count goes up by one (sklearn's loop order: max_iter = 0 is exactly one shift).  The count kept for a seed is |m| of its last shift.  The
+ *       new position depends on the old one only through the member set: with equal member sets rounding does not accumulate over the iterations.
+ *   Centres: the finished seeds with count > 0, sorted descending by (count, tuple(coordinates)) (sklearn's sorted(.., reverse=True)), walked in that order:
+ *       a centre not yet suppressed suppresses every other centre within d2 <= t of it and survives.  The survivors in walk order are cluster_centers_.
+ *   Labels: labels_[j] = the nearest centre by d2 (the centre as the f64 operand), ties to the smaller centre index; with cluster_all = False, -1 where
+ *       d2 > t.  predict is the same rule without orphans.
+ *   Seeds: every point by default, an explicit array, or sklearn's get_bin_seeds.  estimate_bandwidth(X, quantile) = the f64 mean of the k-th neighbour
+ *       distance (dic_knn_kth_distance, the point itself included), k = max(1, int(N quantile)).
+ * X (N, ldx) f32, DEVICE, 16-B aligned, only read; D % 4 == 0 <= 256 (zero-padded columns add nothing), ldx % 4 == 0.  Seeds and centres are packed (rows, D)
+ * f64 on the DEVICE; `centre` (D) f32 is the centre of the bf16 planes ((float)c), `shift` (D) f64 is c.  0 < bandwidth < 2^50.
+ *   dic_meanshift_prepare: the planes of the points in a workspace of dic_meanshift_workspace(N, M_max) bytes (16-B aligned), once per fit; M_max = the most
+ *       seeds one members pass will take (N + M_max + 256 < 2^30).
+ *   dic_meanshift_members: mask (M, ceil(N / 32)) uint32, DEVICE, OVERWRITTEN: bit j & 31 of word j >> 5 of row s is set iff j in m(seed s); bits >= N are
+ *       0.  1 <= M <= M_max.  A pass over (seed, point) tiles on the matrix cores decides every pair whose approximate d2 lies clear of t and lists the rest
+ *       (BAND pairs: band (capacity, 4) int32, DEVICE, 16-B aligned), which a second kernel decides with the exact d2.  More band pairs than `capacity`
+ *       returns DIC_ERR_WORKSPACE with *n_band (HOST) the number needed (mask incomplete; run again with capacity >= *n_band).  Reads *n_band back:
+ *       synchronises `stream`.  The mask is a fixed function of the inputs.
+ *   dic_meanshift_shift: one shift of every seed s < M whose done[s] is 0 (others are left as they are), from its mask row: counts[s] = |m|, and by the rule
+ *       above seeds[s] (IN/OUT), iters[s] (IN/OUT) and done[s] (IN/OUT; zero both before the first shift).  sums (M, D) f64, optional (NULL): the member sums
+ *       sum_j x'_j of the seeds shifted by this call.  A 0/1 by f64 product on the f64 matrix cores, the points in ascending order; no floating-point
+ *       atomics, two calls give the same bits.  Nothing synchronises `stream`.
+ *   dic_meanshift_nearest: for n_rows rows -- X f32 (stride ldx) or R f64 (packed), exactly one non-NULL -- against C >= 1 centres: idx (n_rows) int32 the
+ *       nearest centre, ties to the smaller index, and d2 (n_rows) f64 its exact d2 (each optional, not both NULL).  Nothing synchronises `stream`. */
+size_t dic_meanshift_workspace(int64_t N, int64_t M_max);
+int dic_meanshift_prepare(const float* X, long ldx, int64_t N, int D, const float* centre, int64_t M_max, void* workspace, size_t workspace_bytes,
+                          dic_stream_t stream);
+int dic_meanshift_members(const float* X, long ldx, int64_t N, int D, const float* centre, const double* seeds, int64_t M, int64_t M_max, double bandwidth,
+                          uint32_t* mask, int32_t* band, int64_t capacity, int64_t* n_band, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_meanshift_shift(const float* X, long ldx, int64_t N, int D, const double* shift, const uint32_t* mask, int64_t M, double* seeds, double bandwidth,
+                        int max_iter, int32_t* counts, int32_t* iters, int32_t* done, double* sums, dic_stream_t stream);
+int dic_meanshift_nearest(const float* X, long ldx, const double* R, int64_t n_rows, int D, const double* centres, int C, int32_t* idx, double* d2,
+                          dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
