@@ -149,6 +149,13 @@ SIGNATURES = {
     'dic_meanshift_members': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, C.c_int64, C.c_int64, C.c_double, _p, _p, C.c_int64, _p, _p, _sz, _p]),
     'dic_meanshift_shift': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, C.c_int64, _p, C.c_double, _i, _p, _p, _p, _p, _p]),
     'dic_meanshift_nearest': (_i, [_p, C.c_long, _p, C.c_int64, _i, _p, _i, _p, _p, _p]),
+    'dic_kmedoids_workspace': (_sz, [C.c_int64, _i]),
+    'dic_kmedoids_prepare': (_i, [_p, C.c_long, C.c_int64, _i, _p, _i, _p, _sz, _p]),
+    'dic_kmedoids_assign': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_long, C.c_int64, _p, _i, _p, _p, _p, _p, _p, _p]),
+    'dic_kmedoids_delta_pass': (_i, [C.c_int64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_kmedoids_select': (_i, [C.c_int64, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),
+    'dic_kmedoids_exact': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, _p, _i, _p, _p, _p, _i, _p, _p]),
+    'dic_kmedoids_pick': (_i, [_p, C.c_int64, _p, _p, _i, _p, _p]),
     'dic_optics_workspace': (_sz, [C.c_int64, _i]),
     'dic_optics_order': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_double, _p, _p, _p, _p, _sz, _p]),
     'dic_hdbscan_workspace': (_sz, [C.c_int64, _i]),

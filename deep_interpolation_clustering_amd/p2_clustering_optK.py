@@ -66,6 +66,12 @@ gives centres to carry to the other cohorts.  One fit per bandwidth: --meanshift
 distance to its nearest centre, and the --internal_metrics) goes to <metric>_meanshift_aligned/plot/meanshift_bandwidth.csv, the labels to
 plot/meanshift_labels.csv, one column bw<index> per bandwidth, and the centres to plot/meanshift_centers.csv (bandwidth, cluster, the coordinates), %.17g.
 
+``--cluster_method kmedoids`` (no upstream counterpart): k-medoids (PAM: BUILD, then steepest-descent SWAP) of the training latents on the GPU for
+K = 2..k_max (kmedoids.py: no N x N matrix; an approximate pass on the matrix cores selects swap candidates, an exact f64 stage decides) -- the one family
+whose centres are encounters.  The per-K table (k, inertia = the sum of distances to the nearest medoid, n_iter, converged and the --internal_metrics) goes
+to <metric>_kmedoids_aligned/plot/kmedoids_k.csv, the 0-based labels to plot/kmedoids_labels.csv, one column k<K> per K, and the medoids to
+plot/kmedoids_medoids.csv (k, cluster, the row of the medoid encounter in the training latents, its encounter id).
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -86,6 +92,7 @@ from .hdbscan import hdbscan_sizes
 from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
 from .kmeans import KMeans, seed_draw_count
+from .kmedoids import kmedoids_sweep
 from .meanshift import estimate_bandwidth, mean_shift_sweep
 from .knn import k_distance_graph
 from .optics import OPTICS
@@ -100,7 +107,7 @@ np.random.seed(123)        # p2_clustering_optK.py:23
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids'])
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -654,6 +661,64 @@ class Ward(object):
         return df
 
 
+class Kmedoids(object):
+    """k-medoids (PAM) of the training latents for K = 2..``k_max`` (``kmedoids.kmedoids_sweep``: the planes prepared once, one BUILD of ``k_max`` whose
+    prefixes start every K, SWAP per K).  Per K: TD (``inertia``), the SWAP searches, the convergence flag and the ``internal_metrics`` of the labels as the
+    Ward branch computes them -- one shared pair pass per K, ``metric_sample`` honoured -- logged per K as ``KM`` logs.  Writes plot/kmedoids_k.csv,
+    plot/kmedoids_labels.csv (columns k2..k<k_max>, 0-based) and plot/kmedoids_medoids.csv (k, cluster, the row of the medoid encounter in the training
+    latents, its encounter id) and returns the per-K table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.
+    ``fits_`` keeps the {K: ``kmedoids.KMedoids``} of the last run that computed them."""
+    FILES = ('kmedoids_k.csv', 'kmedoids_labels.csv', 'kmedoids_medoids.csv')
+    COLUMNS = ['k', 'inertia', 'n_iter', 'converged']
+    MEDOID_COLUMNS = ['k', 'cluster', 'medoid_index', 'encounter_id']
+
+    def __init__(self, k_max, out_path, internal_metrics, metric_sample=0):
+        self.ks = list(range(2, k_max + 1))
+        self.metric_sample = metric_sample
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.internal_metrics_names = list(internal_metrics)
+        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
+        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self.fits_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fits_ = None
+        k_csv, labels_csv, medoids_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (k_csv, labels_csv, medoids_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(k_csv))
+            return pd.read_csv(k_csv, float_precision='round_trip')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        fits = kmedoids_sweep(Xd, self.ks)
+        ids = train_data.get('encounter_id') if hasattr(train_data, 'get') else None
+        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
+        rows, medoid_rows = [], []
+        for k in self.ks:
+            logger.info('Running K: {}'.format(k))
+            fit = fits[k]
+            labels = fit.labels_
+            if self.metric_sample and self.metric_sample < len(labels):
+                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
+                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
+            else:
+                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
+                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
+            logger.info('k: {}, inertia: {:.4f}, n_iter: {}, converged: {} '.format(k, fit.inertia_, fit.n_iter_, fit.converged_)
+                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+            rows.append([k, fit.inertia_, fit.n_iter_, int(fit.converged_)] + vals)
+            for slot, at in enumerate(fit.medoid_indices_):
+                medoid_rows.append([k, slot, int(at), ids[int(at)] if ids is not None else ''])
+        df = pd.DataFrame(rows, columns=self.COLUMNS + self.internal_metrics_names)
+        df.to_csv(k_csv, index=False, float_format='%.17g')
+        pd.DataFrame({'k{}'.format(k): fits[k].labels_ for k in self.ks}).to_csv(labels_csv, index=False)
+        pd.DataFrame(medoid_rows, columns=self.MEDOID_COLUMNS).to_csv(medoids_csv, index=False)
+        logger.info('Saved for {}!.'.format(k_csv))
+        self.fits_ = fits
+        return df
+
+
 class Gmm(object):
     """Gaussian mixtures of the training latents (``gmm.gmm_sweep``) for K = 2..``k_max``, ``n_init`` restarts each.  Per K: the lower bound, BIC and AIC on the
     training latents, the iterations and whether the winning restart converged, the mean log-likelihood of the validation cohort under the training model, and
@@ -965,8 +1030,13 @@ class Cluster(object):
                                    self.args.meanshift_bin_seeding, bool(self.args.meanshift_cluster_all), self.args.metric_sample)
                     results[metric] = ms.train(self.train_data, self.valid_data)
                 continue
+            if self.args.cluster_method == 'kmedoids':
+                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
+                    kd = Kmedoids(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.metric_sample)
+                    results[metric] = kd.train(self.train_data, self.valid_data)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan, ward, gmm, snn, spectral and meanshift are on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan, ward, gmm, snn, spectral, meanshift and kmedoids are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

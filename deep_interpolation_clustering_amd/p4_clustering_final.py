@@ -37,6 +37,9 @@ labelled by ``predict`` of that one model; writes <cohort>_<k>.npy with ``cluste
 mean shift fit of the training latents on the GPU (meanshift.py) at --meanshift_bandwidth, or at estimate_bandwidth(training latents,
 --meanshift_quantile); the centres re-numbered by sbp and every cohort labelled by ``predict``, the nearest centre -- with --meanshift_cluster_all 0 an
 encounter farther than the bandwidth from it is an orphan, -1; writes <cohort>_meanshift-bw<bandwidth, %.6g>.npy.
+``kmedoids`` (no upstream counterpart; the kmeans branch with medoids -- actual training encounters -- in place of the centres): one k-medoids (PAM) fit of
+the training latents on the GPU (kmedoids.py) from BUILD with --num_clusters slots, the slots re-numbered by sbp and every cohort labelled by ``predict``, the
+nearest medoid; writes <cohort>_<k>.npy with ``cluster_id`` and, for the training cohort, ``medoid_index``: the rows of the medoid encounters in slot order.
 """
 import argparse
 import copy
@@ -52,6 +55,7 @@ from .gmm import GaussianMixture
 from .hdbscan import HDBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
+from .kmedoids import KMedoids
 from .meanshift import MeanShift, estimate_bandwidth
 from .knn import knn_transfer_labels
 from .snn import SNN
@@ -64,7 +68,7 @@ np.random.seed(123)        # p4_clustering_final.py:24
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
@@ -322,6 +326,31 @@ class Cluster(object):
             np.save(f, data)
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
 
+    def _kmedoids(self, cohorts, overwrite):
+        """The kmeans branch with k-medoids (PAM) in place of k-means: one fit of the training cohort from BUILD, generate_align_map orders the slots by sbp and
+        the medoids are permuted with the map.  Every cohort, training included, is labelled by ``predict`` of that model, the nearest medoid (the training
+        cohort's ``labels_`` are exactly that); the training cohort's file also holds ``medoid_index``, the rows of the medoid encounters in slot order."""
+        k = self.args.num_clusters
+        logger.info('==> Generate the k-medoids results with opt-k: {}'.format(k))
+        model = KMedoids(n_clusters=k).fit(self.train_data['hidden'])
+        raw = np.array(model.labels_)
+        align_map, _, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
+        order = np.empty(k, dtype=np.int64)
+        for old, new in align_map.items():
+            order[new] = old
+        model.reorder(order)
+        for cohort, data in cohorts:
+            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, k))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            data['cluster_id'] = model.predict(data['hidden'])
+            if cohort == 'training':
+                data['medoid_index'] = model.medoid_indices_.copy()
+            del data['ob'], data['padding_mask']
+            np.save(f, data)
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+
     def _raw_consensus(self, cohort, data):
         """The raw consensus labels of a cohort for k = num_clusters, 0-based as generate_align_map wants them (p4:247-253): column k<num_clusters> of
         raw_consensus_result/<cohort>_consensus.csv, computed and written first where the file is missing."""
@@ -424,8 +453,10 @@ class Cluster(object):
                 self._gmm(cohorts, overwrite)
             elif self.args.cluster_method == 'meanshift':
                 self._meanshift(cohorts, overwrite)
+            elif self.args.cluster_method == 'kmedoids':
+                self._kmedoids(cohorts, overwrite)
             else:
-                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus', 'hdbscan' and 'ward' are on the accelerated path: upstream's 'optics' branch of p4 is an "
+                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus', 'hdbscan', 'snn', 'spectral', 'ward', 'gmm', 'meanshift' and 'kmedoids' are on the accelerated path: upstream's 'optics' branch of p4 is an "
                                           "empty `pass` (p2 has the OPTICS fit)")
 
 

@@ -851,6 +851,49 @@ int dic_meanshift_shift(const float* X, long ldx, int64_t N, int D, const double
 int dic_meanshift_nearest(const float* X, long ldx, const double* R, int64_t n_rows, int D, const double* centres, int C, int32_t* idx, double* d2,
                           dic_stream_t stream);
 
+/* k-medoids (PAM) with the Euclidean distance (csrc/dic_kmedoids.hip, kmedoids.py), stated here once.  All arithmetic is f64.
+ *   Distances: d(o, c) = sqrt(exact_d2(x_o, x_c)), exact_d2 as csrc/dic_exactd2.h defines it (the f64 difference form of the f32 rows in its lane order).
+ *   For medoids m_0 .. m_{K-1} (distinct rows of X): n(o) = the slot of the nearest medoid, ties to the smaller slot; dn(o) the distance to it, ds(o) the
+ *       distance to the second nearest (+inf at K = 1); TD = sum_o dn(o).
+ *   BUILD: the first medoid is the c that minimises sum_o d(o, c); each further one is the non-medoid c that minimises
+ *       g(c) = sum_o [min(d(o, c), dn(o)) - dn(o)]; ties to the smaller index.  The BUILD medoids of K are the first K of those of any larger K.
+ *   SWAP: steepest descent (the original PAM's result, with FastPAM1's shared removal term).  Per iteration, for every non-medoid c and every slot i:
+ *       Delta(c, i) = sum_o [min(d(o, c), dn(o)) - dn(o)] + sum_{o: n(o) = i} [min(d(o, c), ds(o)) - min(d(o, c), dn(o))].
+ *       Take the smallest Delta, ties to the smaller c, then the smaller i.  If it is not < 0: stop, converged.  Otherwise c goes into slot i and the next
+ *       iteration starts, up to max_iter iterations.
+ *   Order of the sums over o (two runs give the same bits): TD: a workgroup of 1024 threads, thread t adds dn[t], dn[t + 1024], .. ascending, then a binary
+ *       tree over the 1024 partials (stride 512, 256, .., 1).  g and Delta: 16 waves, wave w adds its terms for o = w, w + 16, .. ascending -- g and, per slot,
+ *       r_i = the second sum -- then g = the waves' g in wave order, r_i likewise, Delta(c, i) = g + r_i.
+ * X (N, ldx) f32, DEVICE, 16-B aligned, only read; D % 4 == 0 <= 256 (zero-padded columns add nothing), ldx % 4 == 0; 1 <= K <= DIC_MAX_CLUSTERS;
+ * N + 256 (K + 2) < 2^30.  medoids (K) int32 row indices, nearest (N) int32, dn / ds (N) f64: all on the DEVICE.  Nothing synchronises `stream`.
+ *   dic_kmedoids_workspace / dic_kmedoids_prepare: the split-bf16 planes of the points (centre (D) f32: their column means) in a workspace of
+ *       dic_kmedoids_workspace(N, K_max) bytes (16-B aligned), once per fit; K_max = the most slots a pass will take.
+ *   dic_kmedoids_assign (exact): for n_rows query rows Q (X itself, or other points: predict) against the K medoid rows of X: nearest, dn, ds and dist
+ *       (n_rows, K) f64 = the distance to every medoid (each optional, not all NULL), and td (1) f64 = sum dn in the order above (optional; needs dn).
+ *   dic_kmedoids_delta_pass (approximate, on the matrix cores): mode 2 (SWAP): g (N) f64 ~ the first sum of Delta, r (N, K) f64 ~ the second sum per slot,
+ *       E (N) f64 with |g[c] + r[c, i] - Delta(c, i)| <= E[c] for every i (also |g - first sum| <= E and |r - second sum| <= E); the derivation stands in
+ *       the source file.  mode 1 (BUILD): g ~ g(c) from dn (nearest, ds, r unused).  mode 0 (first BUILD step): g ~ sum_o d(o, c) (dn unused too).
+ *       Rows of medoids are computed like any other.  The values are for SELECTING candidates only.
+ *   dic_kmedoids_select: v(c) = g[c] + min_{i < cols} r[c, i] (cols = 0: g[c]); U = min over non-medoids of v + E; list (N) int32 receives, in no particular
+ *       order, every non-medoid c with v - E <= U, *count (DEVICE int32) their number.  The exact minimum is always among them.
+ *   dic_kmedoids_exact: for the M candidates cand[0 .. M-1] (cand NULL: c = 0 .. M-1; count non-NULL: only the first *count (DEVICE) of them) the f64
+ *       Delta(c, 0 .. K-1) of the definition into delta (M, K) (mode 2), g(c) into delta (M) (mode 1), sum_o d(o, c) (mode 0), in the order above.
+ *       One workgroup of 16 waves works on one candidate at a time; the workgroups stride over the list, and the order of a candidate's sums is the one
+ *       stated above whatever the grid.
+ *   dic_kmedoids_pick: out (4) f64 DEVICE = {c, i, Delta, entries considered} of the smallest (Delta, c, i) in lexicographic order over delta (M, cols)
+ *       (c = -1 when there is none). */
+size_t dic_kmedoids_workspace(int64_t N, int K_max);
+int dic_kmedoids_prepare(const float* X, long ldx, int64_t N, int D, const float* centre, int K_max, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_kmedoids_assign(const float* Q, long ldq, int64_t n_rows, int D, const float* X, long ldx, int64_t N, const int32_t* medoids, int K, int32_t* nearest,
+                        double* dn, double* ds, double* dist, double* td, dic_stream_t stream);
+int dic_kmedoids_delta_pass(int64_t N, int K_max, int K, int mode, const int32_t* nearest, const double* dn, const double* ds, double* g, double* r, double* E,
+                            void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_kmedoids_select(int64_t N, int K_max, int cols, const double* g, const double* r, const double* E, const int32_t* medoids, int n_medoids, int32_t* list,
+                        int32_t* count, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_kmedoids_exact(const float* X, long ldx, int64_t N, int D, const int32_t* cand, int64_t M, const int32_t* count, int mode, const int32_t* nearest,
+                       const double* dn, const double* ds, int K, double* delta, dic_stream_t stream);
+int dic_kmedoids_pick(const int32_t* cand, int64_t M, const int32_t* count, const double* delta, int cols, double* out, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
