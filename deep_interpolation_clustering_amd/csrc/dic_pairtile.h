@@ -151,13 +151,21 @@ static __global__ __launch_bounds__(256) void pt_block_max_kernel(const float* n
     if (threadIdx.x == 0) bmax[blockIdx.x] = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
 }
 
-// the 256 padding points as operand j: norm `pad_norm` (a power of two: exact in bf16) in the first norm column of pb
-static __global__ __launch_bounds__(256) void pt_pad_norm_kernel(__bf16* pb, int n, float pad_norm) {
-    pb[(size_t)(n + threadIdx.x) * PT_LD + PT_D + 3] = (__bf16)pad_norm;
+// The norm columns of the 256 padding points (their rows are zeroed beforehand): pt_prep_kernel's [n n n 1 | 1 1 ..] and [1 1 1 n | n n ..] with the norm 0
+// as operand i and `pad_norm` (a power of two: exact in bf16) as operand j.  The ones carry the OTHER point's norm pieces: without them a padding point is no
+// zero vector but an absent one -- a_ij = 0 instead of n_j in a padding row, pad_norm alone instead of n_i + pad_norm in a padding column (with
+// PT_PAD_NORM the same f32 value; no epilogue flushes a padding row, and those that pass 0 mask the columns by index, so only tests/test_gpu_pairtile.py can
+// tell the two apart).
+static __global__ __launch_bounds__(256) void pt_pad_rows_kernel(__bf16* pa, __bf16* pb, int n, float pad_norm) {
+    const size_t et = (size_t)(n + threadIdx.x) * PT_LD + PT_D;
+    const __bf16 one = (__bf16)1.f;
+    pa[et + 3] = one; pa[et + 4] = one; pa[et + 5] = one;
+    pb[et] = one; pb[et + 1] = one; pb[et + 2] = one;
+    pb[et + 3] = (__bf16)pad_norm;
 }
 
 // Fills the planes, norms and block maxima of a pt_layout(N) workspace from X (N, D) f32 and the centre (1, D).  The 256 padding rows behind the last point,
-// which the last tiles read, are zero vectors of norm 0 as operand i; as operand j they present the norm pad_norm, so their approximate d^2 is n_i + pad_norm:
+// which the last tiles read, are zero vectors of norm 0 as operand i (a_ij = n_j); as operand j they present the norm pad_norm, so their approximate d^2 is n_i + pad_norm:
 // with 0 an epilogue masks them by index, with a huge value they lie beyond every threshold and need no mask.  (The norm array and the block maxima, which
 // feed the error bound, hold 0 for them either way.)
 static int pt_prepare_planes(const float* X, long ldx, const float* centre, int64_t N, int D, float pad_norm, unsigned char* ws, hipStream_t st,
@@ -173,7 +181,7 @@ static int pt_prepare_planes(const float* X, long ldx, const float* centre, int6
     if (e == hipSuccess) e = hipMemsetAsync(pb + plane + (size_t)N * PT_LD, 0, (size_t)PT_T * PT_LD * sizeof(__bf16), st);
     if (e == hipSuccess) e = hipMemsetAsync(nrm + N, 0, (size_t)PT_T * sizeof(float), st);
     DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "%s: memset: %s", who, hipGetErrorString(e));
-    if (pad_norm != 0.f) hipLaunchKernelGGL(pt_pad_norm_kernel, dim3(1), dim3(256), 0, st, pb, (int)N, pad_norm);
+    hipLaunchKernelGGL(pt_pad_rows_kernel, dim3(1), dim3(256), 0, st, pa, pb, (int)N, pad_norm);
     hipLaunchKernelGGL(pt_prep_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, X, ldx, centre, (int)N, D, pa, pb, plane, nrm);
     const int nblk = (int)((N + PT_T - 1) / PT_T);
     hipLaunchKernelGGL(pt_block_max_kernel, dim3(nblk), dim3(256), 0, st, (const float*)nrm, (int)N, (float*)(ws + o.bmax));

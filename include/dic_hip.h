@@ -646,6 +646,19 @@ size_t dic_knn_neighbors_workspace(int64_t N, int64_t M, int D, int64_t candidat
 int dic_knn_neighbors(const float* X, long ldx, int64_t N, const float* Q, long ldq, int64_t M, const float* centre, int D, int k, double* dist, int32_t* idx,
                       int64_t candidate_budget, int64_t* stats, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* A TEST INSTRUMENT (csrc/dic_pairtile_probe.hip), not an operator: the approximate squared distances a_ij of the shared pair-tile loop (csrc/dic_pairtile.h),
+ * which dic_dbscan_*, dic_knn_*, dic_meanshift_members and dic_kmedoids_delta_pass decide on in registers and never store, written out so that
+ * tests/test_gpu_pairtile.py can hold them to the header's bound |a_ij - d^2_ij| < 2^-12 (n_i + nmax_J).  Nothing in the package calls it.
+ * X, ldx, centre, N, D as for dic_knn_kth_distance (D <= 256, D % 4 == 0, ldx % 4 == 0, 16-B aligned), N <= 65536; nblk = ceil(N / 256).  The planes are
+ * prepared as the consumers prepare them (pad_norm >= 0, a power of two or 0: the norm the 256 padding points present as operand j), then ONE pair pass
+ * walks tiles tile0 .. tile0 + ntiles - 1 of the row-major list of the nblk^2 256 x 256 tiles (ntiles = 0: all from tile0 on) on `grid` workgroups (0: the
+ * consumers' own choice, min(ntiles, 256)).  All DEVICE: out (nblk 256, nblk 256) f32, out[i][j] = a_ij for every (i, j) of a walked tile, padding rows and
+ * columns included, other entries untouched (the caller fills it with NaN beforehand); visits (nblk, nblk) int32, += 1 per walk of tile (I, J) (the caller
+ * zeroes it); nrm (N + 256) f32 and bmax (nblk) f32 OVERWRITTEN = the norms and per-block largest norms the loop's consumers read (0 for padding rows). */
+size_t dic_pairtile_probe_workspace(int64_t N, int D);
+int dic_pairtile_probe(const float* X, long ldx, const float* centre, int64_t N, int D, float pad_norm, int64_t tile0, int64_t ntiles, int grid, float* out,
+                       int32_t* visits, float* nrm, float* bmax, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 /* Shared-nearest-neighbour clustering on the neighbour lists (csrc/dic_snn.hip; Jarvis & Patrick 1973; Ertoz, Steinbach & Kumar 2003); no upstream counterpart.
  * THE DEFINITION, which snn.py, p2, p4 and the tests hold to.  k = n_neighbors, 2 <= k <= min(N, 1024).  L(i) = row i of the self join's idx (N, k) int32 from
  * dic_knn_neighbors: the k index points with the smallest (d^2, index) keys, the point itself an ordinary neighbour (L(i) contains i unless k or more exact
