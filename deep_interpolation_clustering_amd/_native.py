@@ -172,6 +172,11 @@ SIGNATURES = {
     'dic_gmm_em_iter': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _i, _p, _sz, _p]),
     'dic_gmm_estep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'dic_gmm_mstep_labels': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_gmm_full_workspace': (_sz, [C.c_int64, _i, _i, _i, _i]),
+    'dic_gmm_full_em_iter': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _sz, _p]),
+    'dic_gmm_full_estep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_gmm_full_mstep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_gmm_full_factor': (_i, [_p, _i, _i, _i, _i, _p, _p, _p, _p, _sz, _p]),
 }
 
 

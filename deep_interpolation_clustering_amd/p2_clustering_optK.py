@@ -39,7 +39,7 @@ distance to the nearest centre on the training and the validation latents (the e
 <metric>_ward_aligned/plot/ward_k.csv; the dendrogram goes to plot/ward_linkage.csv (scipy's Z, %.17g) and the 0-based labels to plot/ward_labels.csv, one
 column k<K> per K.
 
-``--cluster_method gmm`` (no upstream counterpart): Gaussian mixtures with --gmm_covariance_type diag | spherical covariances, fitted to the training latents on
+``--cluster_method gmm`` (no upstream counterpart): Gaussian mixtures with --gmm_covariance_type diag | spherical | full | tied covariances, fitted to the training latents on
 the GPU for K = 2..k_max with --n_init restarts each (gmm.py: f64 EM, one pass over the latents per iteration, the restarts advancing together).  Per K the
 lower bound, BIC and AIC of the fit itself -- a likelihood-based criterion for K that needs no reference sets -- the iterations, the mean log-likelihood of the
 validation cohort and the --internal_metrics of the hard labels go to <metric>_gmm_aligned/plot/gmm_k.csv, the 0-based labels to plot/gmm_labels.csv, one
@@ -88,6 +88,7 @@ from . import cluster_stats, dist
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
 from .gmm import gmm_sweep
+from .gmm_full import gmm_full_sweep
 from .hdbscan import hdbscan_sizes
 from .info import COHORTS
 from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
@@ -120,7 +121,8 @@ def get_arguments(argv=None):
     p.add_argument('--consensus_p_item', type=float, default=0.8, help='(extra) fraction of the points in a resample')
     p.add_argument('--hdbscan_min_cluster_size', type=int, nargs='+', default=None,
                    help='(extra) min_cluster_size values of --cluster_method hdbscan; default feat_dim + 1')
-    p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical'], help='(extra) covariances of --cluster_method gmm')
+    p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical', 'full', 'tied'],
+                   help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py')
     p.add_argument('--snn_k', type=int, default=None, help='(extra) neighbours per point of --cluster_method snn; default feat_dim + 1')
     p.add_argument('--snn_eps', type=int, nargs='+', default=None,
                    help='(extra) shared-neighbour thresholds of --cluster_method snn, integers in [1, k]; default round(k t / 10) for t = 2..8 -- a starting '
@@ -725,7 +727,7 @@ class Gmm(object):
     the ``internal_metrics`` of the hard labels as ``KM`` computes them -- one shared pair pass per K, ``metric_sample`` honoured -- logged per K as ``KM``
     logs.  Writes plot/gmm_k.csv (k, lower_bound, bic, aic, n_iter, converged, valid_score, the metrics) and plot/gmm_labels.csv (columns k2..k<k_max>,
     0-based) and returns the per-K table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.  ``fits_`` keeps the
-    fitted models {K: ``gmm.GaussianMixture``} of the last run that computed them."""
+    fitted models {K: ``gmm.GaussianMixture`` or ``gmm_full.FullGaussianMixture``} of the last run that computed them."""
     FILES = ('gmm_k.csv', 'gmm_labels.csv')
 
     def __init__(self, k_max, out_path, internal_metrics, n_init=1, covariance_type='diag', metric_sample=0):
@@ -749,7 +751,8 @@ class Gmm(object):
         dev = torch.device('cuda', torch.cuda.current_device())
         Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
         Vd = torch.as_tensor(valid_data['hidden'], dtype=torch.float32, device=dev)
-        fits = gmm_sweep(Xd, self.ks, covariance_type=self.covariance_type, n_init=self.n_init)
+        sweep = gmm_full_sweep if self.covariance_type in ('full', 'tied') else gmm_sweep
+        fits = sweep(Xd, self.ks, covariance_type=self.covariance_type, n_init=self.n_init)
         need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
         rows = []
         for k in self.ks:

@@ -30,8 +30,8 @@ latents on the GPU (consensus.py) and written.
 ``ward`` (no upstream counterpart; the kmeans branch with a tree in place of the fits): the Ward tree of the training latents on the GPU (ward.py) cut at
 --num_clusters, the clusters re-numbered by sbp, the centres re-ordered with the map; the training cohort keeps its tree labels, validation and test get the
 nearest training centre; writes <cohort>_<k>.npy.
-``gmm`` (no upstream counterpart; the kmeans branch with a mixture in place of the centres): a Gaussian mixture of --num_clusters diagonal components fitted
-to the training latents on the GPU (gmm.py), the components re-numbered by sbp -- weights, means and covariances permuted with the map -- and every cohort
+``gmm`` (no upstream counterpart; the kmeans branch with a mixture in place of the centres): a Gaussian mixture of --num_clusters components (--gmm_covariance_type, default
+diag) fitted to the training latents on the GPU (gmm.py; gmm_full.py for full and tied), the components re-numbered by sbp -- weights, means and covariances permuted with the map -- and every cohort
 labelled by ``predict`` of that one model; writes <cohort>_<k>.npy with ``cluster_id`` and ``cluster_prob``, the (N, K) f32 responsibilities.
 ``meanshift`` (no upstream counterpart; the kmeans branch with the modes of the latent density in place of the centres, their number found by the fit): one
 mean shift fit of the training latents on the GPU (meanshift.py) at --meanshift_bandwidth, or at estimate_bandwidth(training latents,
@@ -52,6 +52,7 @@ import pandas as pd
 from . import cluster_stats
 from .dbscan import DBSCAN
 from .gmm import GaussianMixture
+from .gmm_full import FullGaussianMixture
 from .hdbscan import HDBSCAN
 from .info import COHORTS
 from .kmeans import KMeans
@@ -70,6 +71,8 @@ def get_arguments(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
+    p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical', 'full', 'tied'],
+                   help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
     p.add_argument('--hdbscan_min_cluster_size', type=int, default=None, help='(extra) min_cluster_size of --cluster_method hdbscan; default feat_dim + 1')
@@ -273,7 +276,9 @@ class Cluster(object):
         included, is labelled by ``predict`` of that model; ``cluster_prob`` holds its responsibilities, so ``cluster_id`` is their argmax."""
         k = self.args.num_clusters
         logger.info('==> Generate the Gaussian mixture results with opt-k: {}'.format(k))
-        model = GaussianMixture(n_components=k, n_init=10).fit(self.train_data['hidden'])
+        cov = self.args.gmm_covariance_type
+        cls = FullGaussianMixture if cov in ('full', 'tied') else GaussianMixture
+        model = cls(n_components=k, n_init=10, covariance_type=cov).fit(self.train_data['hidden'])
         raw = model.predict(self.train_data['hidden']).astype(np.int64)
         if len(set(raw)) != k:
             raise ValueError('the Gaussian mixture left {} of its {} components without a training encounter: choose a smaller --num_clusters'.format(

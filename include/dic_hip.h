@@ -797,6 +797,50 @@ int dic_gmm_mstep_labels(const float* X, long ldx, int64_t N, int D, int D0, int
                          const int32_t* labels, const double* resp, double* weights, double* means, double* variances, void* workspace,
                          size_t workspace_bytes, dic_stream_t stream);
 
+/* Gaussian mixtures with full (cov_type 2) or tied (cov_type 3) covariances by EM, every operation in f64, the products on the f64 matrix cores
+ * (csrc/dic_gmm_full.hip, gmm_full.py; sklearn.mixture.GaussianMixture's model).  X, D, D0, ldx, N, K, n_runs, shift, weights (n_runs, K) and means
+ * (n_runs, K, D) as for dic_gmm_*: x' = (double)x - shift, `means` holds mu' = mu - shift, the columns D0 .. D - 1 are zero padding.  Kc = K for full and 1 for
+ * tied covariances.  Per restart, f64 on the DEVICE: covariances (n_runs, Kc, D, D), symmetric; prec_chol (n_runs, Kc, D, D), upper triangular (exactly 0 below
+ * the diagonal); log_det (n_runs, Kc).  In the padding (an index >= D0) C and P are the identity: the padding adds exactly 0 to M and to log_det.
+ *   E-step: y_ik = (x'_i - mu'_k) P_k;  M_ik = sum_d y_ikd^2;  log p_ik = log w_k - (D0 log 2 pi + M_ik) / 2 + log_det_k,  log_det_k = sum_{d < D0} log P_k,dd;
+ *       lse_i = max_k log p_ik + log sum_k exp(log p_ik - max) (k in order), log r_ik = log p_ik - lse_i; the lower bound is mean_i lse_i.
+ *   M-step: n_k = sum_i r_ik + 10 * 2^-52;  mu'_k = sum_i r_ik x'_i / n_k;  w_k = (n_k / N) / sum_k (n_k / N).
+ *       full: C_k = S_k / n_k - mu'_k mu'_k^T + reg_covar I,  S_k = sum_i r_ik x'_i x'_i^T.
+ *       tied: C = (T - sum_k n_k mu'_k mu'_k^T) / sum_k n_k + reg_covar I,  T = sum_i x'_i x'_i^T (scatter_total (D, D): it does not depend on r, is formed once
+ *       per fit -- dic_gmm_full_mstep with compute_total != 0 writes it -- and only read afterwards).
+ *       Both are sklearn 1.7.2's _estimate_gaussian_covariances_full / _tied in shifted coordinates and expanded form.
+ *   Factor: C = L L^T, P = L^-T, by columns in this order:  for j = 0 .. D0 - 1:  s_i = C_ij, then s_i = s_i - L_it L_jt for t = 0 .. j - 1 ascending (one rounded
+ *       product, one rounded difference), for every i >= j;  L_jj = sqrt(s_j);  L_ij = s_i / L_jj.  Then for every column j of P, c = j .. 0 descending:
+ *       P_jj = 1 / L_jj;  P_cj = -(sum_{t = c + 1 .. j} L_tc P_tj) / L_cc, the sum from 0.0 with t ascending.  log_det = sum_d log P_dd, d ascending from 0.0.
+ *       A pivot s_j that is not a finite positive number sets the restart's status word [7] to 1 and its done flag [0]; that matrix's P becomes the identity
+ *       and its log_det 0, so nothing downstream reads a NaN, and the other restarts go on.
+ * Sums over rows: the E-step's per-workgroup partials (sum lse, sum_i r_ik, sum_i r_ik x'_i; at most 256 workgroups per restart, their rows a function of N
+ * alone) are added in block order; S_k / T are computed on and below the block diagonal of 16 x 16 tiles per row slab -- slabs(N, m) = max(1, min(ceil(N / 256),
+ * ceil(128 / m))) for m matrices per restart (m = K for S_k, 1 for T): a function of N and K alone -- and the slab matrices are added in slab order by the kernel
+ * that also mirrors the lower triangle, so C == C^T bit for bit.  No floating-point atomics; two calls give the same bits; a restart's bits do not depend on
+ * the restarts beside it; nothing synchronises `stream`.
+ *   dic_gmm_full_workspace: bytes of the workspace (16-B aligned) of the other calls, 0 for arguments outside the limits.  With a256(w) = 8 w rounded up to 256,
+ *       B = min(256, ceil(N / 64)) workgroups and R = n_runs:  a256(R N K) [log r] + a256(R B (K (D + 1) + 1)) [partials] + a256(R K) [n_k]
+ *       + a256(R K slabs(N, K) D^2) (full) or a256(slabs(N, 1) D^2) (tied) [slab matrices] + a256(R Kc D^2) [L^T of the factor].
+ *   dic_gmm_full_em_iter: one E+M pass, factor included, for every restart whose done flag is clear.  status and lower_bounds as dic_gmm_em_iter, and
+ *       status[7] = 1 after an ill-defined covariance.
+ *   dic_gmm_full_estep: the E-step of ONE parameter set; the optional outputs of dic_gmm_estep.
+ *   dic_gmm_full_mstep: the M-step, factor included, from hard labels (n_runs, N) int32 or responsibilities (n_runs, N, K) f64 -- exactly one.  status
+ *       (n_runs, DIC_GMM_STATUS_WORDS): only [0] and [7] are written, after an ill-defined covariance.
+ *   dic_gmm_full_factor: covariances (n_runs, n_mats, D, D) -> prec_chol, log_det, status[0] / [7]; its workspace is 8 n_runs n_mats D^2 bytes. */
+size_t dic_gmm_full_workspace(int64_t N, int D, int K, int n_runs, int cov_type);
+int dic_gmm_full_em_iter(const float* X, long ldx, int64_t N, int D, int D0, int K, int n_runs, int cov_type, double reg_covar, const double* shift,
+                         double* weights, double* means, double* covariances, double* prec_chol, double* log_det, const double* scatter_total, double* status,
+                         double* lower_bounds, int lb_stride, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_gmm_full_estep(const float* X, long ldx, int64_t N, int D, int D0, int K, int cov_type, const double* shift, const double* weights, const double* means,
+                       const double* prec_chol, const double* log_det, double* lse, double* log_resp, int32_t* labels, double* sum_lse, void* workspace,
+                       size_t workspace_bytes, dic_stream_t stream);
+int dic_gmm_full_mstep(const float* X, long ldx, int64_t N, int D, int D0, int K, int n_runs, int cov_type, double reg_covar, const double* shift,
+                       const int32_t* labels, const double* resp, double* scatter_total, int compute_total, double* weights, double* means, double* covariances,
+                       double* prec_chol, double* log_det, double* status, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_gmm_full_factor(const double* covariances, int n_runs, int n_mats, int D, int D0, double* prec_chol, double* log_det, double* status, void* workspace,
+                        size_t workspace_bytes, dic_stream_t stream);
+
 /* Spectral clustering on the symmetrised k-neighbour graph (csrc/dic_spectral.hip, spectral.py): sklearn 1.7.2's
  * SpectralClustering(affinity='nearest_neighbors'), stated here once.
  *   L(i): the list of the k nearest neighbours of point i from dic_knn_neighbors, self join (the point itself its first entry), 2 <= k.  A: the 0/1 matrix of
