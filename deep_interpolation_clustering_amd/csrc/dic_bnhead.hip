@@ -15,23 +15,30 @@
 
 namespace dic {
 
-// 8 consecutive columns of a row of z as floats: one 16-B load of bf16 (the bf16 step) or two of f32 (the f32 step: the `_f32` entry points)
+// 8 consecutive columns of a row of z as floats: one 16-B load of bf16 (the bf16 step) or two of f32 (the f32 step: the `_f32` entry points).
+// Raw8 is the same piece as it arrives from memory: the load rings of the forward and the backward reduction hold their row sets in this
+// form (4 registers per bf16 piece instead of 8) and widen a piece only when its turn comes; the widening is exact, so the order changes no bit.
 typedef float bnf32x4 __attribute__((ext_vector_type(4)));
 struct Row8 { float v[8]; };
-__device__ __forceinline__ Row8 load_row8(const __bf16* p) {
-    const bf16x8 x = *reinterpret_cast<const bf16x8*>(p);
+template <typename ZT> struct Raw8;
+template <> struct Raw8<__bf16> { bf16x8 x; };
+template <> struct Raw8<float> { bnf32x4 a, b; };
+__device__ __forceinline__ Raw8<__bf16> load_raw8(const __bf16* p) { return {*reinterpret_cast<const bf16x8*>(p)}; }
+__device__ __forceinline__ Raw8<float> load_raw8(const float* p) { return {*reinterpret_cast<const bnf32x4*>(p), *reinterpret_cast<const bnf32x4*>(p + 4)}; }
+__device__ __forceinline__ Row8 to_row8(const Raw8<__bf16>& q) {
     Row8 r;
 #pragma unroll
-    for (int e = 0; e < 8; ++e) r.v[e] = (float)x[e];
+    for (int e = 0; e < 8; ++e) r.v[e] = (float)q.x[e];
     return r;
 }
-__device__ __forceinline__ Row8 load_row8(const float* p) {
-    const bnf32x4 a = *reinterpret_cast<const bnf32x4*>(p), b = *reinterpret_cast<const bnf32x4*>(p + 4);
+__device__ __forceinline__ Row8 to_row8(const Raw8<float>& q) {
     Row8 r;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { r.v[e] = a[e]; r.v[4 + e] = b[e]; }
+    for (int e = 0; e < 4; ++e) { r.v[e] = q.a[e]; r.v[4 + e] = q.b[e]; }
     return r;
 }
+template <typename ZT>
+__device__ __forceinline__ Row8 load_row8(const ZT* p) { return to_row8(load_raw8(p)); }
 __device__ __forceinline__ void store_row8(__bf16* p, const float (&o)[8]) {
     bf16x8 x;
 #pragma unroll
@@ -111,6 +118,41 @@ __global__ __launch_bounds__(BK) void bn_moments_kernel(const double* sums, floa
     }
 }
 
+// Load rings of the forward and the backward reduction.  A lane keeps AHEAD row sets requested beyond the one it is working on, in
+// SLOTS = AHEAD + 1 fixed register sets: trip t works on slot t % SLOTS and first requests trip t + AHEAD into the slot trip t - 1 has
+// just left.  The trip loop is unrolled by SLOTS, so no piece is ever copied from one set to another (a copy waits for its piece).
+// The bf16 forward of up to eight columns runs 3-4 waves per SIMD and has room for three raw pieces; the backward reduction holds ~220
+// registers at 2 waves per SIMD, and three pieces + dv rows (235 registers at six columns) is as deep as its bf16 form of up to six
+// columns goes without scratch or a lost wave; the f32 and wider forms keep one row set ahead.  The compiler's waits are what decides
+// how much of that is in flight: see docs/history.md for the counts read off the ISA.
+// What the generated code needs for the ring to hold (a wait that allows fewer loads than the ring keeps in flight empties it):
+//  - every request is unconditional, from a clamped and therefore valid row (a load under a condition lands in a fresh register set);
+//  - the per-lane constants have arrived before the first request (settle_loads);
+//  - the loop has ONE way out, at the end of a round, on a 32-bit scalar count of rounds (wave_trips).  Every further exit is routed
+//    through the block in front of the loop's head, and a pending ring load on that path (or a 64-bit compare of row and N there, which
+//    goes through a vector register pair -- one a ring load is still due in) puts a full wait on the back edge.  The trips of the last
+//    round that are past the end are skipped under a scalar condition, their requests still issued (from the clamped row);
+//  - nothing per-lane decides whether a trip runs: around a trip under a vector condition the register allocator splits the ring's live
+//    ranges and copies each piece right behind its load.  The reduction therefore takes the grid's one ragged row set after the loop.
+template <int C, typename ZT>
+constexpr int fwd_ahead() { return (sizeof(ZT) == 2 && C <= 8) ? 3 : 1; }
+template <int C, typename ZT>
+constexpr int bwd_reduce_ahead() { return (sizeof(ZT) == 2 && C <= 6) ? 3 : 1; }
+
+// Trips of the wave whose first row is row0 (rows row0, row0 + stride, ... below N), as a 32-bit scalar
+__device__ __forceinline__ int wave_trips(long row0, long N, long stride) {
+    return __builtin_amdgcn_readfirstlane(row0 < N ? (int)((unsigned long)(N - row0 + stride - 1) / (unsigned long)stride) : 0);
+}
+
+// Every load issued so far has arrived.  Stands between the loads of a kernel's per-lane constants and its row loop: vector loads
+// return in order, so a wait for a constant placed inside the loop (where the compiler puts it, at the first use) allows only as many
+// loads in flight as were issued after that constant before the loop was entered -- fewer than the ring holds in steady state.
+__device__ __forceinline__ void settle_loads() {
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0), the other counters left alone
+    asm volatile("" ::: "memory");
+}
+
 template <int C, typename ZT>
 __global__ __launch_bounds__(256) void bnhead_fwd_kernel(const ZT* z, const float* mean, const float* rstd, const float* gamma,
                                                          const float* beta, const float* W, const float* b, long N, float floor_, float drop_p,
@@ -136,14 +178,17 @@ __global__ __launch_bounds__(256) void bnhead_fwd_kernel(const ZT* z, const floa
         a += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a), 0xB1, 0xF, 0xF, false));      // quad_perm [1,0,3,2]
         return a;
     };
-    long row0 = ((long)blockIdx.x * 4 + wave) * 4;
-    Row8 xn = {};
-    if (row0 + slot < N) xn = load_row8(z + (row0 + slot) * BK + kc * 8);
-    for (; row0 < N; row0 += stride) {       // wave-uniform trip count; the next row is in flight while this one is reduced
+    // ring of this lane's row sets as raw pieces (see fwd_ahead); rows past the end are requested from the last row and never stored
+    constexpr int AHEAD = fwd_ahead<C, ZT>(), SLOTS = AHEAD + 1;
+    settle_loads();
+    long row0 = ((long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wave)) * 4;      // the wave's first row, in scalar registers
+    Raw8<ZT> ring[SLOTS] = {};
+#pragma unroll
+    for (int s = 0; s < AHEAD; ++s) ring[s] = load_raw8(z + min(row0 + slot + s * stride, N - 1) * BK + kc * 8);
+    auto trip = [&](const Raw8<ZT>& piece) __attribute__((always_inline)) {
         const long row = row0 + slot;
         const bool live = row < N;
-        const Row8 x = xn;
-        if (row + stride < N) xn = load_row8(z + (row + stride) * BK + kc * 8);
+        const Row8 x = to_row8(piece);
         float acc[C], keep[8];
         drop_factors(drop, row, kc, keep);
 #pragma unroll
@@ -161,6 +206,17 @@ __global__ __launch_bounds__(256) void bnhead_fwd_kernel(const ZT* z, const floa
             if (kc == j) out = a;
         }
         if (live && kc < C) v[row * C + kc] = out + bias;
+        row0 += stride;
+    };
+    int left = wave_trips(row0, N, stride);
+    for (int rounds = (left + SLOTS - 1) / SLOTS; rounds > 0; --rounds) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const bool on = left > 0;
+            --left;
+            ring[(s + AHEAD) % SLOTS] = load_raw8(z + min(row0 + slot + AHEAD * stride, N - 1) * BK + kc * 8);
+            if (on) trip(ring[s]);
+        }
     }
 }
 
@@ -206,24 +262,23 @@ __global__ __launch_bounds__(256) void bnhead_bwd_reduce_kernel(const ZT* z, con
         for (int e = 0; e < 8; ++e) accw[j][e] = 0.f;
     }
     const long stride = (long)gridDim.x * 16;
-    long row = ((long)blockIdx.x * 4 + wave) * 4 + slot;
-    Row8 xn = {};
-    float gn[C] = {};
-    if (row < N) {
-        xn = load_row8(z + row * BK + kc * 8);
+    // ring of this lane's rows, the raw 16-B piece of z and the C floats of dv each (see fwd_ahead); rows past the end are requested from
+    // the last row and never used.  A lane still takes its rows in the order row, row + stride, ...: only the distance between a row's
+    // request and its use has grown, so every partial sum is formed as before
+    constexpr int AHEAD = bwd_reduce_ahead<C, ZT>(), SLOTS = AHEAD + 1;
+    settle_loads();
+    long row0 = ((long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(wave)) * 4, row = row0 + slot;      // row0: the wave's first row, in scalar registers
+    Raw8<ZT> xr[SLOTS] = {};
+    float gr[SLOTS][C] = {};
 #pragma unroll
-        for (int j = 0; j < C; ++j) gn[j] = dv[row * C + j];
+    for (int s = 0; s < AHEAD; ++s) {
+        const long r = min(row + s * stride, N - 1);
+        xr[s] = load_raw8(z + r * BK + kc * 8);
+#pragma unroll
+        for (int j = 0; j < C; ++j) gr[s][j] = dv[r * C + j];
     }
-    for (; row < N; row += stride) {
-        const Row8 x = xn;
-        float g[C];
-#pragma unroll
-        for (int j = 0; j < C; ++j) g[j] = gn[j];
-        if (row + stride < N) {              // next row in flight while this one is reduced
-            xn = load_row8(z + (row + stride) * BK + kc * 8);
-#pragma unroll
-            for (int j = 0; j < C; ++j) gn[j] = dv[(row + stride) * C + j];
-        }
+    auto trip = [&](const Raw8<ZT>& piece, const float (&g)[C]) __attribute__((always_inline)) {
+        const Row8 x = to_row8(piece);
         float h[8], xhat[8], da[8];
         float keep[8];
         drop_factors(drop, row, kc, keep);
@@ -239,6 +294,30 @@ __global__ __launch_bounds__(256) void bnhead_bwd_reduce_kernel(const ZT* z, con
 #pragma unroll
             for (int e = 0; e < 8; ++e) accw[j][e] = fmaf(g[j], h[e], accw[j][e]);
         }
+        row += stride;
+    };
+    // the wave's trips on whole row sets (all four rows below N) run through the ring under scalar control only; the one ragged set the
+    // grid can have follows the loop as each of its lanes' last row, loaded on the spot
+    int left = wave_trips(row0, N - 3, stride);
+    for (int rounds = (left + SLOTS - 1) / SLOTS; rounds > 0; --rounds) {
+#pragma unroll
+        for (int s = 0; s < SLOTS; ++s) {
+            const bool on = left > 0;
+            --left;
+            const int sn = (s + AHEAD) % SLOTS;
+            const long r = min(row + AHEAD * stride, N - 1);
+            xr[sn] = load_raw8(z + r * BK + kc * 8);
+#pragma unroll
+            for (int j = 0; j < C; ++j) gr[sn][j] = dv[r * C + j];
+            if (on) trip(xr[s], gr[s]);
+        }
+    }
+    if (row < N) {
+        const Raw8<ZT> xl = load_raw8(z + row * BK + kc * 8);
+        float gl[C];
+#pragma unroll
+        for (int j = 0; j < C; ++j) gl[j] = dv[row * C + j];
+        trip(xl, gl);
     }
     // fold the 4 row slots of the wave (lanes l, l^16, l^32, l^48 hold the same columns)
     auto fold4 = [](float a) {

@@ -116,24 +116,31 @@ __global__ __launch_bounds__(512) void fc_bwd_kernel(FcBwdArgs a) {
         }
         for (int i = tid; i < C * FO; i += 512) w2s[i] = a.w2[i];
     }
-    auto request = [&](int tile) {           // (loads from clamped, always valid rows; the rows past the end are zeroed by a select)
+    // (loads from clamped, always valid rows.  The pieces stay as they arrive until `land`, a whole tile later, zeroes the rows past the end:
+    // a select on a piece here is its first use, and the wait for it would stand right behind the load -- nothing would be in flight
+    // while the tile in LDS is multiplied)
+    long pr0 = 0;
+    auto request = [&](int tile) {
         const long r0 = (long)tile * FT;
         const long rz = min(r0 + zrow, N - 1), ra = min(r0 + xrow, N - 1), rb = min(r0 + xrow + 16, N - 1);
-        const uint4 vz = *reinterpret_cast<const uint4*>((FUSED ? a.z : a.dz) + (size_t)rz * FO + zpc * 8);
+        pz = *reinterpret_cast<const uint4*>((FUSED ? a.z : a.dz) + (size_t)rz * FO + zpc * 8);
         if constexpr (FUSED) {
             prow = r0 + zrow;
 #pragma unroll
             for (int j = 0; j < C; ++j) pg[j] = a.dv[(size_t)rz * C + j];
         }
-        const uint4 va = *reinterpret_cast<const uint4*>(a.x + (size_t)ra * FI + xpc * 8);
-        const uint4 vb = *reinterpret_cast<const uint4*>(a.x + (size_t)rb * FI + xpc * 8);
-        const bool kz = r0 + zrow < N, ka = r0 + xrow < N, kb = r0 + xrow + 16 < N;
-        pz = make_uint4(kz ? vz.x : 0u, kz ? vz.y : 0u, kz ? vz.z : 0u, kz ? vz.w : 0u);
-        px0 = make_uint4(ka ? va.x : 0u, ka ? va.y : 0u, ka ? va.z : 0u, ka ? va.w : 0u);
-        px1 = make_uint4(kb ? vb.x : 0u, kb ? vb.y : 0u, kb ? vb.z : 0u, kb ? vb.w : 0u);
+        px0 = *reinterpret_cast<const uint4*>(a.x + (size_t)ra * FI + xpc * 8);
+        px1 = *reinterpret_cast<const uint4*>(a.x + (size_t)rb * FI + xpc * 8);
+        pr0 = r0;
     };
     auto land = [&](int slot) {
         unsigned char* base = fsm + slot * F_TILE;
+        {
+            const bool kz = pr0 + zrow < N, ka = pr0 + xrow < N, kb = pr0 + xrow + 16 < N;
+            pz = make_uint4(kz ? pz.x : 0u, kz ? pz.y : 0u, kz ? pz.z : 0u, kz ? pz.w : 0u);
+            px0 = make_uint4(ka ? px0.x : 0u, ka ? px0.y : 0u, ka ? px0.z : 0u, ka ? px0.w : 0u);
+            px1 = make_uint4(kb ? px1.x : 0u, kb ? px1.y : 0u, kb ? px1.z : 0u, kb ? px1.w : 0u);
+        }
         if constexpr (FUSED) {
             // da = (dv W2) keep 1[h > floor]   (dic_bnhead.hip: recompute_row + bwd B, the mean terms folded into ca + cb z)
             const fbf16x8 x = __builtin_bit_cast(fbf16x8, pz);
@@ -198,7 +205,7 @@ __global__ __launch_bounds__(512) void fc_bwd_kernel(FcBwdArgs a) {
     if (tile + nwg < ntiles) request(tile + nwg);
     __syncthreads();
     int slot = 0;
-    auto store_rows = [&](int st_slot, long r0) {             // the dX block of a tile: staging -> global, whole 512-B rows
+    auto store_rows = [&](int st_slot, long r0) {             // the dX block of a tile: staging -> global, whole 512-B rows (r0 < 0: no tile yet)
         if (!a.dx || r0 < 0) return;
         const unsigned char* sb = stage + st_slot * F_STAGE;
 #pragma unroll
@@ -230,8 +237,15 @@ __global__ __launch_bounds__(512) void fc_bwd_kernel(FcBwdArgs a) {
             }
         }
         // ---- next tile's pieces -> the other image, the one after that requested; this tile's dX block -> staging
-        if (tile + nwg < ntiles) land(slot ^ 1);
-        if (tile + 2 * nwg < ntiles) request(tile + 2 * nwg);
+        // (the request stands inside the landing's condition: on a path that skipped the landing the compiler would have to assume pieces in
+        // flight where the request overwrites them, and waits there for every load and row store)
+        if (tile + nwg < ntiles) {
+            land(slot ^ 1);
+            if (tile + 2 * nwg < ntiles) request(tile + 2 * nwg);
+        }
+        // the previous tile's dX rows leave here, behind the landing: vector stores and loads retire in order, so in front of it (right
+        // after the barrier that ends a tile) the landing's wait for its pieces was also a wait for these stores, issued moments before
+        store_rows(slot ^ 1, (long)(tile - nwg) * FT);
         if (a.dx) {
             // accumulators 2p, 2p + 1 of a lane are rows m, m + 1 of its column: the even lane of a pair takes both columns of row m, the odd
             // lane those of row m + 1 (one quad_perm [1,0,3,2] swap), each stores ONE packed dword
@@ -257,9 +271,9 @@ __global__ __launch_bounds__(512) void fc_bwd_kernel(FcBwdArgs a) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        store_rows(slot, (long)tile * FT);
         slot ^= 1;
     }
+    store_rows(slot ^ 1, (long)(tile - nwg) * FT);           // the last tile's rows
     // C/D layout of the 32x32 tile: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
     float* o = a.partials + (size_t)blockIdx.x * FO * FI;
 #pragma unroll
