@@ -158,6 +158,10 @@ SIGNATURES = {
     'dic_kmedoids_select': (_i, [C.c_int64, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),
     'dic_kmedoids_exact': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, _p, _i, _p, _p, _p, _i, _p, _p]),
     'dic_kmedoids_pick': (_i, [_p, C.c_int64, _p, _p, _i, _p, _p]),
+    'dic_dpeaks_workspace': (_sz, [C.c_int64, _i]),
+    'dic_dpeaks_prepare': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, _sz, _p]),
+    'dic_dpeaks_delta': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_dpeaks_border': (_i, [C.c_int64, _i, _f, _p, _p, _i, _p, C.c_int64, _p, _p, _sz, _p]),
     'dic_optics_workspace': (_sz, [C.c_int64, _i]),
     'dic_optics_order': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_double, _p, _p, _p, _p, _sz, _p]),
     'dic_hdbscan_workspace': (_sz, [C.c_int64, _i]),

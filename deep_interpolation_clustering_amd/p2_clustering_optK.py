@@ -72,6 +72,13 @@ whose centres are encounters.  The per-K table (k, inertia = the sum of distance
 to <metric>_kmedoids_aligned/plot/kmedoids_k.csv, the 0-based labels to plot/kmedoids_labels.csv, one column k<K> per K, and the medoids to
 plot/kmedoids_medoids.csv (k, cluster, the row of the medoid encounter in the training latents, its encounter id).
 
+``--cluster_method densitypeaks`` (no upstream counterpart): density-peaks clustering (Rodriguez and Laio 2014) of the training latents on the GPU
+(density_peaks.py: no N x N matrix) -- the one family that shows a picture from which the number of phenotypes is read.  ONE computation of rho (--dp_density
+cutoff | knn; d_c = --dp_dc or the --dp_percent rule), delta and parent; the decision graph goes to <metric>_densitypeaks_aligned/plot/
+densitypeaks_decision.csv (index, rho, delta, gamma, parent for every point, %.17g), the per-K table for K = 2..--dp_k (default k_max) to
+plot/densitypeaks_k.csv (k, gamma_gap = gamma_(K) / gamma_(K+1), sizes, n_halo and the --internal_metrics of the labels without the halo) and the 0-based
+labels, -1 for halo points with --dp_halo 1, to plot/densitypeaks_labels.csv, one column k<K> per K.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -87,6 +94,7 @@ import torch
 from . import cluster_stats, dist
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
+from .density_peaks import density_peaks_sweep
 from .gmm import gmm_sweep
 from .gmm_full import gmm_full_sweep
 from .hdbscan import hdbscan_sizes
@@ -108,7 +116,7 @@ np.random.seed(123)        # p2_clustering_optK.py:23
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids', 'densitypeaks'])
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -138,6 +146,12 @@ def get_arguments(argv=None):
     p.add_argument('--meanshift_bin_seeding', action='store_true', help="(extra) seed --cluster_method meanshift from sklearn's bins, not from every point")
     p.add_argument('--meanshift_cluster_all', type=int, default=1, choices=[1, 0],
                    help='(extra) 0: a point farther than the bandwidth from its nearest centre is an orphan (-1)')
+    p.add_argument('--dp_density', default='cutoff', choices=['cutoff', 'knn'], help='(extra) density of --cluster_method densitypeaks')
+    p.add_argument('--dp_percent', type=float, default=2.0,
+                   help='(extra) --cluster_method densitypeaks: d_c is the radius at which a point has on average this percentage of the cohort as neighbours')
+    p.add_argument('--dp_dc', type=float, default=None, help='(extra) d_c of --cluster_method densitypeaks; overrides --dp_percent')
+    p.add_argument('--dp_k', type=int, default=None, help='(extra) the largest K of --cluster_method densitypeaks; default k_max')
+    p.add_argument('--dp_halo', type=int, default=0, choices=[0, 1], help='(extra) 1: halo points of --cluster_method densitypeaks are labelled -1 (cutoff only)')
     p.add_argument('--metric_sample', type=int, default=0, help='(extra) subsample size for the O(N^2) validity indices; 0 = all')
     return p.parse_args(argv)
 
@@ -721,6 +735,65 @@ class Kmedoids(object):
         return df
 
 
+class Densitypeaks(object):
+    """Density peaks of the training latents (``density_peaks.density_peaks_sweep``: ONE device computation of rho, delta and parent, one cut per K = 2..
+    ``k_max`` on the host).  Writes plot/densitypeaks_decision.csv (index, rho, delta, gamma, parent: the decision graph, every point), plot/densitypeaks_k.csv
+    (k, gamma_gap, sizes -- the cluster sizes without the halo, joined by blanks --, n_halo and the ``internal_metrics`` of the labels without the halo, as the
+    Ward branch computes them, ``metric_sample`` honoured) and plot/densitypeaks_labels.csv (columns k2..k<k_max>, 0-based, -1 for halo points) and returns
+    the per-K table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.  ``fits_`` keeps the
+    {K: ``density_peaks.DensityPeaks``} of the last run that computed them."""
+    FILES = ('densitypeaks_decision.csv', 'densitypeaks_k.csv', 'densitypeaks_labels.csv')
+    COLUMNS = ['k', 'gamma_gap', 'sizes', 'n_halo']
+    DECISION_COLUMNS = ['index', 'rho', 'delta', 'gamma', 'parent']
+
+    def __init__(self, k_max, out_path, internal_metrics, density='cutoff', percent=2.0, dc=None, halo=False, metric_sample=0):
+        self.ks = list(range(2, k_max + 1))
+        self.kw = dict(density=density, percent=percent, dc='auto' if dc is None else dc, halo=bool(halo))
+        self.metric_sample = metric_sample
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.internal_metrics_names = list(internal_metrics)
+        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
+        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self.fits_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fits_ = None
+        decision_csv, k_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (decision_csv, k_csv, labels_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(k_csv))
+            return pd.read_csv(k_csv, float_precision='round_trip')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        fits = density_peaks_sweep(Xd, self.ks, **self.kw)
+        first = fits[self.ks[0]]
+        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
+        rows = []
+        for k in self.ks:
+            logger.info('Running K: {}'.format(k))
+            fit = fits[k]
+            labels = fit.core_labels_
+            if self.metric_sample and self.metric_sample < len(labels):
+                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
+                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
+            else:
+                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
+                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
+            sizes = np.bincount(labels, minlength=k)
+            logger.info('k: {}, gamma gap: {:.4f}, sizes: {}, halo: {} '.format(k, fit.gamma_gap_, sizes.tolist(), int(fit.halo_.sum()))
+                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+            rows.append([k, fit.gamma_gap_, ' '.join(str(int(v)) for v in sizes), int(fit.halo_.sum())] + vals)
+        df = pd.DataFrame(rows, columns=self.COLUMNS + self.internal_metrics_names)
+        pd.DataFrame({'index': np.arange(len(first.rho_)), 'rho': first.rho_, 'delta': first.delta_, 'gamma': first.gamma_,
+                      'parent': first.parent_}).to_csv(decision_csv, index=False, float_format='%.17g')
+        df.to_csv(k_csv, index=False, float_format='%.17g')
+        pd.DataFrame({'k{}'.format(k): fits[k].labels_ for k in self.ks}).to_csv(labels_csv, index=False)
+        logger.info('Saved for {}!.'.format(k_csv))
+        self.fits_ = fits
+        return df
+
+
 class Gmm(object):
     """Gaussian mixtures of the training latents (``gmm.gmm_sweep``) for K = 2..``k_max``, ``n_init`` restarts each.  Per K: the lower bound, BIC and AIC on the
     training latents, the iterations and whether the winning restart converged, the mean log-likelihood of the validation cohort under the training model, and
@@ -1038,8 +1111,14 @@ class Cluster(object):
                     kd = Kmedoids(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.metric_sample)
                     results[metric] = kd.train(self.train_data, self.valid_data)
                 continue
+            if self.args.cluster_method == 'densitypeaks':
+                if dist.rank() == 0:            # one computation, on rank 0; the other ranks wait at main's barrier
+                    dp = Densitypeaks(self.args.dp_k if self.args.dp_k is not None else self.args.k_max, self.out_path, self.args.internal_metrics,
+                                      self.args.dp_density, self.args.dp_percent, self.args.dp_dc, bool(self.args.dp_halo), self.args.metric_sample)
+                    results[metric] = dp.train(self.train_data, self.valid_data)
+                continue
             if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan, ward, gmm, snn, spectral, meanshift and kmedoids are on the accelerated path")
+                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan, ward, gmm, snn, spectral, meanshift, kmedoids and densitypeaks are on the accelerated path")
             km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
                     self.args.metric_sample)
             results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)

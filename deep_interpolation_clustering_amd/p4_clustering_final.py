@@ -40,6 +40,11 @@ encounter farther than the bandwidth from it is an orphan, -1; writes <cohort>_m
 ``kmedoids`` (no upstream counterpart; the kmeans branch with medoids -- actual training encounters -- in place of the centres): one k-medoids (PAM) fit of
 the training latents on the GPU (kmedoids.py) from BUILD with --num_clusters slots, the slots re-numbered by sbp and every cohort labelled by ``predict``, the
 nearest medoid; writes <cohort>_<k>.npy with ``cluster_id`` and, for the training cohort, ``medoid_index``: the rows of the medoid encounters in slot order.
+``densitypeaks`` (no upstream counterpart; the kmedoids branch with the density peaks -- again training encounters -- as centres): one density-peaks fit of
+the training latents on the GPU (density_peaks.py) at --num_clusters (--dp_k overrides it), density --dp_density (cutoff | knn), d_c = --dp_dc or the
+--dp_percent rule, --dp_halo 1 marking the halo encounters -1; the slots re-numbered by sbp; the training cohort keeps the fit's labels, the other cohorts
+take the nearest centre (``predict``) or, with --transfer knn, the vote among their nearest training encounters; writes <cohort>_<k>[_knn].npy with
+``cluster_id`` and, for the training cohort, ``center_index``: the rows of the centre encounters in slot order.
 """
 import argparse
 import copy
@@ -51,6 +56,7 @@ import pandas as pd
 
 from . import cluster_stats
 from .dbscan import DBSCAN
+from .density_peaks import DensityPeaks
 from .gmm import GaussianMixture
 from .gmm_full import FullGaussianMixture
 from .hdbscan import HDBSCAN
@@ -69,7 +75,7 @@ np.random.seed(123)        # p4_clustering_final.py:24
 
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids'])
+    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids', 'densitypeaks'])
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical', 'full', 'tied'],
                    help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py')
@@ -91,6 +97,12 @@ def get_arguments(argv=None):
     p.add_argument('--meanshift_bin_seeding', action='store_true', help="(extra) seed --cluster_method meanshift from sklearn's bins, not from every point")
     p.add_argument('--meanshift_cluster_all', type=int, default=1, choices=[1, 0],
                    help='(extra) 0: an encounter farther than the bandwidth from its nearest centre is an orphan (-1), in every cohort')
+    p.add_argument('--dp_density', default='cutoff', choices=['cutoff', 'knn'], help='(extra) density of --cluster_method densitypeaks')
+    p.add_argument('--dp_percent', type=float, default=2.0,
+                   help='(extra) --cluster_method densitypeaks: d_c is the radius at which a point has on average this percentage of the cohort as neighbours')
+    p.add_argument('--dp_dc', type=float, default=None, help='(extra) d_c of --cluster_method densitypeaks; overrides --dp_percent')
+    p.add_argument('--dp_k', type=int, default=None, help='(extra) clusters of --cluster_method densitypeaks; default --num_clusters')
+    p.add_argument('--dp_halo', type=int, default=0, choices=[0, 1], help='(extra) 1: halo encounters of --cluster_method densitypeaks are labelled -1 (cutoff only)')
     p.add_argument('--transfer', default='centre', choices=['centre', 'knn'],
                    help="(extra) how --cluster_method dbscan / hdbscan / snn / spectral label the validation and test cohorts: 'centre' fits each cohort and maps its clusters onto "
                         "the nearest training centre (upstream); 'knn' fits the training cohort only and votes among the nearest training encounters")
@@ -356,6 +368,41 @@ class Cluster(object):
             np.save(f, data)
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
 
+    def _densitypeaks(self, cohorts, overwrite):
+        """The kmedoids branch with density peaks in place of PAM: one fit of the training cohort, generate_align_map orders the slots by sbp (from the
+        labels without the halo) and the model is permuted with the map.  The training cohort keeps the fit's ``labels_``; the other cohorts take
+        ``predict``, the nearest centre, or with --transfer knn the vote among the nearest training encounters.  The training cohort's file also holds
+        ``center_index``, the rows of the centre encounters in slot order."""
+        a = self.args
+        k = a.dp_k if getattr(a, 'dp_k', None) is not None else a.num_clusters
+        knn = getattr(a, 'transfer', 'centre') == 'knn'
+        logger.info('==> Generate the density-peaks results with k: {}, density: {}'.format(k, a.dp_density))
+        model = DensityPeaks(n_clusters=k, density=a.dp_density, dc='auto' if a.dp_dc is None else a.dp_dc, percent=a.dp_percent,
+                             halo=bool(a.dp_halo)).fit(self.train_data['hidden'])
+        align_map, _, _ = self.generate_align_map(np.array(model.core_labels_), self.train_data['ob'], self.train_data['padding_mask'])
+        order = np.empty(k, dtype=np.int64)
+        for old, new in align_map.items():
+            order[new] = old
+        model.reorder(order)
+        train_ref = (np.asarray(self.train_data['hidden']), np.array(model.labels_))
+        for cohort, data in cohorts:
+            f = osp.join(self.out_path, '{}_{}{}.npy'.format(cohort, k, '_knn' if knn else ''))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            if cohort == 'training':
+                data['cluster_id'] = model.labels_.copy()
+                data['center_index'] = model.center_indices_.copy()
+                if knn:
+                    data['cluster_vote'] = np.ones(len(model.labels_), dtype=np.float32)
+            elif knn:
+                data['cluster_id'], data['cluster_vote'] = self._knn_labels(None, train_ref, data['hidden'])
+            else:
+                data['cluster_id'] = model.predict(data['hidden'])
+            del data['ob'], data['padding_mask']
+            np.save(f, data)
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+
     def _raw_consensus(self, cohort, data):
         """The raw consensus labels of a cohort for k = num_clusters, 0-based as generate_align_map wants them (p4:247-253): column k<num_clusters> of
         raw_consensus_result/<cohort>_consensus.csv, computed and written first where the file is missing."""
@@ -404,8 +451,8 @@ class Cluster(object):
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         transfer = getattr(self.args, 'transfer', 'centre')          # (an args object from before the flag: the default)
-        if transfer != 'centre' and self.args.cluster_method not in ('dbscan', 'hdbscan', 'snn', 'spectral'):
-            raise ValueError("--transfer {} applies to --cluster_method dbscan and hdbscan only (and to snn and spectral, which follow their branch): '{}' labels every cohort with its training model "
+        if transfer != 'centre' and self.args.cluster_method not in ('dbscan', 'hdbscan', 'snn', 'spectral', 'densitypeaks'):
+            raise ValueError("--transfer {} applies to --cluster_method dbscan and hdbscan only (and to snn, spectral and densitypeaks): '{}' labels every cohort with its training model "
                              "already".format(transfer, self.args.cluster_method))
         for metric in self.args.restore_metric:
             self.feat_path = osp.join(self.exp_path, 'out_feat', metric)
@@ -460,8 +507,10 @@ class Cluster(object):
                 self._meanshift(cohorts, overwrite)
             elif self.args.cluster_method == 'kmedoids':
                 self._kmedoids(cohorts, overwrite)
+            elif self.args.cluster_method == 'densitypeaks':
+                self._densitypeaks(cohorts, overwrite)
             else:
-                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus', 'hdbscan', 'snn', 'spectral', 'ward', 'gmm', 'meanshift' and 'kmedoids' are on the accelerated path: upstream's 'optics' branch of p4 is an "
+                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus', 'hdbscan', 'snn', 'spectral', 'ward', 'gmm', 'meanshift', 'kmedoids' and 'densitypeaks' are on the accelerated path: upstream's 'optics' branch of p4 is an "
                                           "empty `pass` (p2 has the OPTICS fit)")
 
 

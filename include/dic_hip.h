@@ -951,6 +951,38 @@ int dic_kmedoids_exact(const float* X, long ldx, int64_t N, int D, const int32_t
                        const double* dn, const double* ds, int K, double* delta, dic_stream_t stream);
 int dic_kmedoids_pick(const int32_t* cand, int64_t M, const int32_t* count, const double* delta, int cols, double* out, dic_stream_t stream);
 
+/* Density-peaks clustering (Rodriguez and Laio, Science 2014; csrc/dic_dpeaks.hip, density_peaks.py), stated here once.
+ *   Distances: d(i, j) = sqrt(exact_d2(x_i, x_j)), exact_d2 as csrc/dic_exactd2.h defines it (the f64 difference form of the f32 rows), the root in f64.
+ *   Density, one of two:  'cutoff': rho_i = |N_dc(i)| - 1 (an integer), N_dc(i) DBSCAN's neighbour set of eps = d_c, the point itself included
+ *       (dic_dbscan_counts with one eps; threshold and band rules unchanged).  'knn': rho_i = 1 / (1 + kth_i / mean(kth)) in f64 on the host, kth_i the
+ *       distance to the k-th neighbour, the point itself counted (dic_knn_kth_distance).
+ *   Density order: i is denser than j iff rho_i > rho_j, or rho_i == rho_j and i < j: a strict total order; rank_i = i's position in it, rank 0 the densest.
+ *   delta and parent: for rank_i > 0, delta_i = min d(i, j) over the denser j, and parent_i = the minimiser of the key (exact_d2(i, j), rank_j): ties in the
+ *       exact distance go to the denser point.  For the densest point delta = max_j d(i, j) and parent = -1.  gamma_i = rho_i delta_i.
+ *   Centres: n_clusters = K takes the K largest gamma, ties to the smaller rank; or rho_min / delta_min take every point with rho > rho_min and
+ *       delta > delta_min, and the densest point is always added.  Cluster ids are 0 .. K-1 in the order of the centres' ranks.
+ *   Labels: a centre's root is itself, every other point takes its parent's root (parents have smaller rank: every chain ends).
+ *   Halo ('cutoff' only): a border pair is (i, j) with label_i != label_j and j in N_dc(i); border2[c] = max (rho_i + rho_j) over the border pairs with
+ *       label_i = c (an integer; 0 when c has none); i is halo iff 2 rho_i < border2[label_i] (strict, as the paper's published code).
+ * The kernels take X in DENSITY ORDER (row r = the point of rank r: "denser" is col < row), except dic_dpeaks_border.  X (N, ldx) f32, DEVICE, 16-B aligned,
+ * only read; D % 4 == 0 <= 256 (zero-padded columns add nothing), ldx % 4 == 0; 1 <= N < 2^30.  Two calls give the same bits.
+ *   dic_dpeaks_workspace / dic_dpeaks_prepare: the split-bf16 planes of the sorted points (centre (D) f32: the f64 column means cast to f32) in a workspace of
+ *       dic_dpeaks_workspace(N, D) bytes (16-B aligned); does not synchronise.
+ *   dic_dpeaks_delta: on the prepared workspace: delta (N) f64 and parent (N) int32, both DEVICE and in rank space (parent[0] = -1).  cand (capacity, 4)
+ *       int32 DEVICE receives the candidate pairs (row, column, the bits of their exact_d2 as two words): every pair the approximate products cannot exclude
+ *       from being its row's minimum -- the true minimisers are always among them, and the exact stage alone supplies values and decides ties.  *n_cand (HOST)
+ *       = their number; more than `capacity` returns DIC_ERR_WORKSPACE with *n_cand the number needed (nothing written to delta / parent: run again with
+ *       capacity >= *n_cand).  stats (2) int64 HOST = {candidates, the longest row's}.  Reads counts back: synchronises `stream`.
+ *   dic_dpeaks_border: border2 (n_clusters) int32 DEVICE of the definition from labels (N) int32 in [0, n_clusters) and rho (N) int32, DEVICE, in the
+ *       ORIGINAL row order, on the workspace a dic_dbscan_counts call of the same points with the one threshold (the f32 squared-distance threshold of d_c)
+ *       left, with its band list (n_band entries, exact masks in .z).  Does not synchronise. */
+size_t dic_dpeaks_workspace(int64_t N, int D);
+int dic_dpeaks_prepare(const float* X, long ldx, int64_t N, int D, const float* centre, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_dpeaks_delta(const float* X, long ldx, int64_t N, int D, int32_t* cand, int64_t capacity, double* delta, int32_t* parent, int64_t* n_cand,
+                     int64_t* stats, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_dpeaks_border(int64_t N, int D, float threshold, const int32_t* labels, const int32_t* rho, int n_clusters, const int32_t* band, int64_t n_band,
+                      int32_t* border2, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
