@@ -162,6 +162,12 @@ SIGNATURES = {
     'dic_dpeaks_prepare': (_i, [_p, C.c_long, C.c_int64, _i, _p, _p, _sz, _p]),
     'dic_dpeaks_delta': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, _p, _p, _p, _p, _p, _sz, _p]),
     'dic_dpeaks_border': (_i, [C.c_int64, _i, _f, _p, _p, _i, _p, C.c_int64, _p, _p, _sz, _p]),
+    'dic_tsne_perplexity': (_i, [_p, C.c_int64, _i, C.c_double, _p, _p, _p]),
+    'dic_tsne_splits': (_i, [C.c_int64]),
+    'dic_tsne_repulsion_workspace': (_sz, [C.c_int64]),
+    'dic_tsne_repulsion': (_i, [_p, C.c_int64, _p, _sz, _p]),
+    'dic_tsne_step_partials': (C.c_int64, [C.c_int64]),
+    'dic_tsne_step': (_i, [_p, _p, _p, C.c_int64, C.c_int64, _p, _p, _sz, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p]),
     'dic_optics_workspace': (_sz, [C.c_int64, _i]),
     'dic_optics_order': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_double, _p, _p, _p, _p, _sz, _p]),
     'dic_hdbscan_workspace': (_sz, [C.c_int64, _i]),

@@ -79,6 +79,11 @@ densitypeaks_decision.csv (index, rho, delta, gamma, parent for every point, %.1
 plot/densitypeaks_k.csv (k, gamma_gap = gamma_(K) / gamma_(K+1), sizes, n_halo and the --internal_metrics of the labels without the halo) and the 0-based
 labels, -1 for halo points with --dp_halo 1, to plot/densitypeaks_labels.csv, one column k<K> per K.
 
+``--embed tsne`` (no upstream counterpart; beside any --cluster_method): one exact t-SNE fit of the training latents on the GPU (tsne.py: --tsne_perplexity,
+default 30, --tsne_max_iter, default 1000, init 'pca') -- the two-dimensional map every plot/*_labels.csv above can be drawn on.  The map goes to
+<metric>_<method>_aligned/plot/tsne.csv (x, y as %.17g, one row per training encounter in the cohort's row order) and the error at every check to
+plot/tsne_kl.csv (iteration, kl).  Without --embed nothing changes.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -108,6 +113,7 @@ from .optics import OPTICS
 from .snn import snn_sweep
 from ._native import MAX_CLUSTERS
 from .spectral import spectral_sweep
+from .tsne import TSNE
 from .utils import logger, print_dict_byline
 from .ward import Ward as WardLinkage
 
@@ -153,6 +159,10 @@ def get_arguments(argv=None):
     p.add_argument('--dp_k', type=int, default=None, help='(extra) the largest K of --cluster_method densitypeaks; default k_max')
     p.add_argument('--dp_halo', type=int, default=0, choices=[0, 1], help='(extra) 1: halo points of --cluster_method densitypeaks are labelled -1 (cutoff only)')
     p.add_argument('--metric_sample', type=int, default=0, help='(extra) subsample size for the O(N^2) validity indices; 0 = all')
+    p.add_argument('--embed', default=None, choices=['tsne'],
+                   help='(extra) also write a two-dimensional map of the training latents (plot/tsne.csv) that every plot/*_labels.csv can be drawn on')
+    p.add_argument('--tsne_perplexity', type=float, default=30.0, help="(extra) perplexity of --embed tsne; default 30, sklearn's")
+    p.add_argument('--tsne_max_iter', type=int, default=1000, help="(extra) iterations of --embed tsne; default 1000, sklearn's (250 of them exaggerated)")
     return p.parse_args(argv)
 
 
@@ -986,6 +996,38 @@ class Spectral(object):
         return df
 
 
+class Tsne(object):
+    """--embed tsne: one exact t-SNE fit of the training latents (``tsne.TSNE``: init 'pca', ``perplexity``, ``max_iter`` iterations).  Writes plot/tsne.csv
+    (x, y as %.17g, one row per training encounter in the cohort's row order -- the order of every plot/*_labels.csv) and plot/tsne_kl.csv (iteration, kl:
+    the error at every check, every 50 iterations, and at the last iteration) and returns the latter table.  Existing files are left alone unless
+    ``overwrite`` is set; the table on disk is returned then.  ``fit_`` keeps the fitted ``TSNE`` of the last run that computed one."""
+    FILES = ('tsne.csv', 'tsne_kl.csv')
+
+    def __init__(self, out_path, perplexity=30.0, max_iter=1000):
+        self.perplexity, self.max_iter = perplexity, max_iter
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.fit_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fit_ = None
+        map_csv, kl_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if all(osp.exists(f) for f in (map_csv, kl_csv)) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(map_csv))
+            return pd.read_csv(kl_csv, float_precision='round_trip')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        fit = TSNE(perplexity=self.perplexity, max_iter=self.max_iter, init='pca').fit(Xd)
+        logger.info('t-SNE with perplexity: {}, n_iter: {}, kl: {:.6f}'.format(self.perplexity, fit.n_iter_, fit.kl_divergence_))
+        pd.DataFrame({'x': fit.embedding_[:, 0], 'y': fit.embedding_[:, 1]}).to_csv(map_csv, index=False, float_format='%.17g')
+        df = pd.DataFrame(fit.kl_history_, columns=['iteration', 'kl'])
+        df.to_csv(kl_csv, index=False, float_format='%.17g')
+        logger.info('Saved for {}!.'.format(map_csv))
+        self.fit_ = fit
+        return df
+
+
 class Consensus(object):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
@@ -1053,6 +1095,9 @@ class Cluster(object):
             self.out_path = osp.join(self.exp_path, 'out_feat', '{}_{}'.format(metric, self.args.cluster_method)) + '_aligned'
             os.makedirs(self.out_path, exist_ok=True)
             self.load_data()
+            if getattr(self.args, 'embed', None) == 'tsne' and dist.rank() == 0:          # (an args object from before the flag: no map)
+                # one fit, on rank 0, beside whatever --cluster_method writes; it draws nothing from numpy's global stream
+                Tsne(self.out_path, self.args.tsne_perplexity, self.args.tsne_max_iter).train(self.train_data, self.valid_data)
             if self.args.cluster_method == 'dbscan':
                 if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
                     eps_range = np.arange(.5, 5.1, .5)

@@ -45,6 +45,9 @@ the training latents on the GPU (density_peaks.py) at --num_clusters (--dp_k ove
 --dp_percent rule, --dp_halo 1 marking the halo encounters -1; the slots re-numbered by sbp; the training cohort keeps the fit's labels, the other cohorts
 take the nearest centre (``predict``) or, with --transfer knn, the vote among their nearest training encounters; writes <cohort>_<k>[_knn].npy with
 ``cluster_id`` and, for the training cohort, ``center_index``: the rows of the centre encounters in slot order.
+``--embed tsne`` (no upstream counterpart; beside any --cluster_method): one exact t-SNE fit of the training cohort on the GPU (tsne.py: --tsne_perplexity,
+--tsne_max_iter); the validation and test cohorts are PLACED on that map by ``transform`` -- every encounter at the p-weighted mean of its nearest training
+encounters' positions -- not embedded again; writes <cohort>_tsne.npy with ``encounter_id``, ``hidden`` and ``tsne`` (N, 2) f64.  Without --embed nothing changes.
 """
 import argparse
 import copy
@@ -67,6 +70,7 @@ from .meanshift import MeanShift, estimate_bandwidth
 from .knn import knn_transfer_labels
 from .snn import SNN
 from .spectral import SpectralClustering
+from .tsne import TSNE
 from .utils import logger, print_dict_byline
 from .ward import Ward
 
@@ -108,6 +112,10 @@ def get_arguments(argv=None):
                         "the nearest training centre (upstream); 'knn' fits the training cohort only and votes among the nearest training encounters")
     p.add_argument('--transfer_k', type=int, default=None, help='(extra) neighbours of --transfer knn; default feat_dim + 1')
     p.add_argument('--dl_cluster_label_type', default='pred', choices=['label', 'pred'])
+    p.add_argument('--embed', default=None, choices=['tsne'],
+                   help='(extra) also write a two-dimensional map of every cohort (<cohort>_tsne.npy): one fit of the training cohort, the others placed on it')
+    p.add_argument('--tsne_perplexity', type=float, default=30.0, help="(extra) perplexity of --embed tsne; default 30, sklearn's")
+    p.add_argument('--tsne_max_iter', type=int, default=1000, help="(extra) iterations of --embed tsne; default 1000, sklearn's (250 of them exaggerated)")
     return p.parse_args(argv)
 
 
@@ -403,6 +411,25 @@ class Cluster(object):
             np.save(f, data)
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
 
+    def _embed_tsne(self, cohorts, overwrite):
+        """--embed tsne: one exact t-SNE fit of the training cohort (tsne.py: init 'pca', --tsne_perplexity, --tsne_max_iter); the validation and test
+        cohorts are PLACED on that map by ``transform`` (every encounter at the p-weighted mean of its nearest training encounters' positions), not
+        embedded again.  Writes <cohort>_tsne.npy: ``encounter_id``, ``hidden`` and ``tsne`` (N, 2) f64, in the cohort's row order."""
+        files = [osp.join(self.out_path, '{}_tsne.npy'.format(cohort)) for cohort, _ in cohorts]
+        if all(osp.exists(f) for f in files) and not overwrite:
+            logger.info('Not Save for {}.'.format(files[0]))
+            return
+        logger.info('==> Generate the t-SNE map with perplexity: {}'.format(self.args.tsne_perplexity))
+        model = TSNE(perplexity=self.args.tsne_perplexity, max_iter=self.args.tsne_max_iter, init='pca').fit(self.train_data['hidden'])
+        logger.info('t-SNE n_iter: {}, kl: {:.6f}'.format(model.n_iter_, model.kl_divergence_))
+        for (cohort, data), f in zip(cohorts, files):
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            tsne = model.embedding_.copy() if cohort == 'training' else model.transform(data['hidden'])
+            np.save(f, {'encounter_id': data['encounter_id'], 'hidden': data['hidden'], 'tsne': tsne})
+            logger.info('Cohort map: {} is done. Save to {}'.format(cohort, f))
+
     def _raw_consensus(self, cohort, data):
         """The raw consensus labels of a cohort for k = num_clusters, 0-based as generate_align_map wants them (p4:247-253): column k<num_clusters> of
         raw_consensus_result/<cohort>_consensus.csv, computed and written first where the file is missing."""
@@ -460,6 +487,8 @@ class Cluster(object):
             os.makedirs(self.out_path, exist_ok=True)
             self.load_data()
             cohorts = list(zip(COHORTS, [self.train_data, self.valid_data, self.test_data]))
+            if getattr(self.args, 'embed', None) == 'tsne':          # (an args object from before the flag: no map)
+                self._embed_tsne(cohorts, overwrite)
             if self.args.cluster_method == 'kmeans':
                 k = self.args.num_clusters
                 logger.info('==> Generate the k-means results with opt-k: {}'.format(k))

@@ -983,6 +983,40 @@ int dic_dpeaks_delta(const float* X, long ldx, int64_t N, int D, int32_t* cand, 
 int dic_dpeaks_border(int64_t N, int D, float threshold, const int32_t* labels, const int32_t* rho, int n_clusters, const int32_t* band, int64_t n_band,
                       int32_t* border2, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* Exact t-SNE in two dimensions (csrc/dic_tsne.hip, tsne.py): sklearn 1.7.2's TSNE(method='exact') on its neighbour-based affinities, stated here once.
+ * All arithmetic is f64.
+ *   Affinities: k = min(N - 1, int(3 perplexity + 1)); L(i) = the k nearest neighbours of i without i itself (dic_knn_neighbors, self join with k + 1, the
+ *       entry of the row's own index dropped, the first entry where it is not among them); r_ij = d_ij^2 - min_j d_ij^2.  beta_i is found by sklearn's
+ *       search: beta = 1, no bounds; per step p_j = exp(-beta r_ij), s = sum p, H = log s + beta (sum r p) / s; stop if |H - log perplexity| <= 1e-10 or
+ *       at the 200th evaluation; else H too large: lower bound = beta and beta doubles while there is no upper bound, else the midpoint; H too small: upper
+ *       bound = beta and beta halves while there is no lower bound, else the midpoint.  p_j|i = p_j / s and beta_i are those of the LAST evaluation (a
+ *       row whose nearest entries are all at distance 0 and the step cap end there).  P_ij = (p_j|i + p_i|j) / sum over all pairs of the same.
+ *   Map: Y (N, 2).  q_ij = 1 / (1 + |y_i - y_j|^2) for i != j, Z = sum_{i != j} q_ij, Q = q / Z.  With the exaggeration e:
+ *       grad_i = 4 (sum_j e P_ij q_ij (y_i - y_j) - (sum_{j != i} q_ij^2 (y_i - y_j)) / Z);  KL = e (sum P log P + log e + sum P log(1 + d^2) + log Z).
+ *   Update (sklearn's _gradient_descent): gains += 0.2 where update * grad < 0, else *= 0.8; gains >= 0.01; update = momentum update - lr (grad gains);
+ *       Y += update.  250 iterations at e = early_exaggeration and momentum 0.5, then e = 1 and momentum 0.8; the checks run every 50 iterations.
+ * Everything is on the DEVICE; no floating-point atomics; two calls give the same bits; nothing synchronises `stream`.  2 <= N < 2^30.
+ *   dic_tsne_perplexity: d2 (M, k) row-major = r (the row minimum already subtracted), 1 <= k <= 1024, perplexity > 0: beta (M) and p (M, k) OVERWRITTEN.
+ *       One wave per row; the sums of a step are per-lane sums over the entries lane, lane + 64, .. ascending, then the xor tree 32, 16, .., 1.
+ *   dic_tsne_repulsion: for the map Y (N, 2), 16-B aligned, leaves in the workspace (dic_tsne_repulsion_workspace(N) bytes, 16-B aligned): Z at double 0,
+ *       and behind it, per column split s < S = dic_tsne_splits(N), the partial sums over the split's columns of q^2 (y_i - y_j) (x, y) and of q.  The
+ *       splits, the 256-column chunks and the 64-column piece each of the four waves takes are functions of N alone; a wave adds its columns in ascending
+ *       order, the four waves are added in wave order, the splits in split order by the consumer.  1 / (1 + d^2) is an f32 reciprocal refined by two f64
+ *       Newton steps (relative error of a few 2^-53).  The pair (i, i) and the padding of the last block contribute exactly nothing.  |y| < 1e18.
+ *   dic_tsne_step: on that workspace and the symmetric CSR of P (indptr (N + 1) int64, indices (nnz) int32, pval (nnz) f64; an entry outside [0, N) is
+ *       absent, indptr is clamped to [0, nnz]): the gradient of the definition -- per row the lane sums over entries lane, lane + 64, .. ascending by fma,
+ *       then the xor tree -- written to grad (N, 2) (optional), and with update, gains (N, 2, IN/OUT) and Ynew (N, 2, OVERWRITTEN, never Y) non-NULL the
+ *       update rule: Ynew = Y + update.  All three NULL: the gradient alone.  partials (dic_tsne_step_partials(N), 2) OVERWRITTEN: per workgroup of four
+ *       rows the sums of |grad_i|^2 and of sum_j P_ij log(1 + d_ij^2) in row order; the host adds them when it checks progress. */
+int dic_tsne_perplexity(const double* d2, int64_t M, int k, double perplexity, double* beta, double* p, dic_stream_t stream);
+int dic_tsne_splits(int64_t N);
+size_t dic_tsne_repulsion_workspace(int64_t N);
+int dic_tsne_repulsion(const double* Y, int64_t N, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int64_t dic_tsne_step_partials(int64_t N);
+int dic_tsne_step(const int64_t* indptr, const int32_t* indices, const double* pval, int64_t N, int64_t nnz, const double* Y, const void* workspace,
+                  size_t workspace_bytes, double exaggeration, double momentum, double learning_rate, double* update, double* gains, double* Ynew,
+                  double* grad, double* partials, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
