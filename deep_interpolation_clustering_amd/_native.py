@@ -138,6 +138,8 @@ SIGNATURES = {
     'dic_knn_kth_distance': (_i, [_p, C.c_long, _p, C.c_int64, _i, C.c_int64, _p, C.c_int64, _p, _p, _sz, _p]),
     'dic_knn_neighbors_workspace': (_sz, [C.c_int64, C.c_int64, _i, C.c_int64]),
     'dic_knn_neighbors': (_i, [_p, C.c_long, C.c_int64, _p, C.c_long, C.c_int64, _p, _i, _i, _p, _p, C.c_int64, _p, _p, _sz, _p]),
+    'dic_knn_ranks_workspace': (_sz, [C.c_int64, _i, _i, C.c_int64]),
+    'dic_knn_ranks': (_i, [_p, C.c_long, _p, C.c_int64, _i, _p, _i, _p, C.c_int64, _p, _p, _sz, _p]),
     'dic_pairtile_probe_workspace': (_sz, [C.c_int64, _i]),
     'dic_pairtile_probe': (_i, [_p, C.c_long, _p, C.c_int64, _i, _f, C.c_int64, C.c_int64, _i, _p, _p, _p, _p, _p, _sz, _p]),
     'dic_snn_similarity': (_i, [_p, C.c_int64, _i, _p, _p]),

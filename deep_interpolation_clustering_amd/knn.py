@@ -10,6 +10,9 @@ Neighbour LISTS come from the same file (``dic_knn_neighbors``): ``kneighbors`` 
 of a set against itself or of a query set against an index set; ``NearestNeighbors`` wraps it in sklearn's interface (``kneighbors``, ``kneighbors_graph`` as
 CSR triples), and ``knn_transfer_labels`` is the uniform vote of ``KNeighborsClassifier`` -- the out-of-sample labels p4 gives DBSCAN and HDBSCAN with
 ``--transfer knn``.
+
+Neighbour RANKS come from csrc/dic_knn_rank.hip (``dic_knn_ranks``): ``neighbor_ranks`` says where given points stand among a row's neighbours, the quantity
+trustworthiness and continuity (embedding_quality.py) are sums of.
 """
 from __future__ import annotations
 
@@ -127,6 +130,58 @@ def kneighbors(X, k, Q=None, candidate_budget=None, stats=None, return_device=Fa
     if return_device:
         return dist, idx
     return dist.cpu().numpy(), idx.cpu().numpy()
+
+
+MAX_TARGETS = 1023          # csrc/dic_knn_rank.hip: KR_MAXM, the targets of a row the exact stage tallies in LDS
+
+
+def neighbor_ranks(X, targets, candidate_budget=None, stats=None, return_device=False):
+    """``ranks (N, m) int32``: where ``targets[i, q]`` stands among the neighbours of row i of ``X`` -- the counterpart of ``kneighbors``, which gives the
+    neighbour at a rank.  ``rank = 1 + #{l != i : (d2(i, l), l) < (d2(i, j), j)}`` (include/dic_hip.h, dic_knn_ranks): the 1-based position of j in row i of
+    ``kneighbors(X, N)[1]`` after the row's own index is dropped, d2 the f64 difference-form squared distance of the f32 coordinates, ties in distance
+    settled by the smaller index.  A target equal to its row's index or negative (absent) has rank 0.  ``X`` (N, D): a numpy array or tensor, D <= 256;
+    ``targets`` (N, m): integers below N, m <= 1023.  Nothing N x N is stored (csrc/dic_knn_rank.hip).  numpy result, or a device tensor with
+    ``return_device=True``.  ``candidate_budget`` and ``stats`` as for ``kneighbors`` (8 bytes per pair the approximate pass cannot place; ``passes`` counts
+    the counting passes, one per 8 targets): the budget never changes the result."""
+    n, dx = _shape_of(X)
+    tshape = tuple(targets.shape) if hasattr(targets, 'shape') else np.asarray(targets).shape
+    if len(tshape) != 2:
+        raise ValueError('targets must be 2-D (n_samples, n_targets), got shape %s' % (tshape,))
+    if n < 1:
+        raise ValueError('Found array with 0 sample(s) (shape=(%d, %d)) while a minimum of 1 is required.' % (n, dx))
+    if tshape[0] != n:
+        raise ValueError('Found input variables with inconsistent numbers of samples: [%d, %d]' % (n, tshape[0]))
+    m = int(tshape[1])
+    if m < 1:
+        raise ValueError('Expected n_targets > 0. Got %d' % m)
+    if m > MAX_TARGETS:
+        raise NotImplementedError('neighbor_ranks: at most %d targets per row (got %d)' % (MAX_TARGETS, m))
+    budget = 0 if candidate_budget is None else int(candidate_budget)
+    if candidate_budget is not None and budget < 1:
+        raise ValueError('candidate_budget must be positive, got %r' % (candidate_budget,))
+    if dx > MAX_DIM:
+        raise NotImplementedError('neighbor_ranks: at most %d features (got %d)' % (MAX_DIM, dx))
+    tt = torch.as_tensor(targets)
+    if tt.dtype.is_floating_point or tt.dtype == torch.bool or tt.dtype.is_complex:
+        raise ValueError('targets must be integers, got %s' % (tt.dtype,))
+    x = _device_points(X)
+    tt = tt.to(x.device)
+    if int(tt.max()) >= n:
+        raise ValueError('targets must be below n_samples = %d (negative: absent), got %d' % (n, int(tt.max())))
+    tt = tt.clamp(min=-1).to(torch.int32).contiguous()
+    d = x.shape[1]
+    L = N.lib()
+    ws = torch.empty(max(16, L.dic_knn_ranks_workspace(n, d, m, budget)), dtype=torch.uint8, device=x.device)
+    ranks = torch.empty((n, m), dtype=torch.int32, device=x.device)
+    centre = x.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
+    st = (N.C.c_int64 * len(STAT_NAMES))()
+    rc = L.dic_knn_ranks(N.ptr(x), x.stride(0), N.ptr(centre), n, d, N.ptr(tt), m, N.ptr(ranks), budget, st, N.ptr(ws), ws.numel(), N.stream_of(x))
+    if stats is not None:
+        stats.update(zip(STAT_NAMES, (int(v) for v in st)))
+    if rc == -3 and st[4] > 0:          # DIC_ERR_WORKSPACE: one row's bands alone are longer than the budget
+        raise CandidateBudgetError('neighbor_ranks: %s' % L.dic_last_error_string().decode(), st[4])
+    N.check(rc, 'dic_knn_ranks')
+    return ranks if return_device else ranks.cpu().numpy()
 
 
 class NearestNeighbors:

@@ -82,7 +82,9 @@ labels, -1 for halo points with --dp_halo 1, to plot/densitypeaks_labels.csv, on
 ``--embed tsne`` (no upstream counterpart; beside any --cluster_method): one exact t-SNE fit of the training latents on the GPU (tsne.py: --tsne_perplexity,
 default 30, --tsne_max_iter, default 1000, init 'pca') -- the two-dimensional map every plot/*_labels.csv above can be drawn on.  The map goes to
 <metric>_<method>_aligned/plot/tsne.csv (x, y as %.17g, one row per training encounter in the cohort's row order) and the error at every check to
-plot/tsne_kl.csv (iteration, kl).  Without --embed nothing changes.
+plot/tsne_kl.csv (iteration, kl).  Without --embed nothing changes.  ``--embed_quality_k 5 10 30`` (with --embed tsne) also says whether the map's
+neighbourhoods can be believed (embedding_quality.py): plot/tsne_quality.csv (k, trustworthiness, continuity, neighbors_kept as %.17g, one row per k), the
+figures that are comparable across perplexities, which kl is not.  Without that flag no such file is written.
 
 The seaborn plots of the upstream script are not provided.
 """
@@ -163,6 +165,9 @@ def get_arguments(argv=None):
                    help='(extra) also write a two-dimensional map of the training latents (plot/tsne.csv) that every plot/*_labels.csv can be drawn on')
     p.add_argument('--tsne_perplexity', type=float, default=30.0, help="(extra) perplexity of --embed tsne; default 30, sklearn's")
     p.add_argument('--tsne_max_iter', type=int, default=1000, help="(extra) iterations of --embed tsne; default 1000, sklearn's (250 of them exaggerated)")
+    p.add_argument('--embed_quality_k', type=int, nargs='+', default=None,
+                   help='(extra) with --embed tsne: also write trustworthiness, continuity and the share of neighbours kept of the map at these '
+                        'neighbourhood sizes (plot/tsne_quality.csv), e.g. 5 10 30')
     return p.parse_args(argv)
 
 
@@ -1000,11 +1005,15 @@ class Tsne(object):
     """--embed tsne: one exact t-SNE fit of the training latents (``tsne.TSNE``: init 'pca', ``perplexity``, ``max_iter`` iterations).  Writes plot/tsne.csv
     (x, y as %.17g, one row per training encounter in the cohort's row order -- the order of every plot/*_labels.csv) and plot/tsne_kl.csv (iteration, kl:
     the error at every check, every 50 iterations, and at the last iteration) and returns the latter table.  Existing files are left alone unless
-    ``overwrite`` is set; the table on disk is returned then.  ``fit_`` keeps the fitted ``TSNE`` of the last run that computed one."""
+    ``overwrite`` is set; the table on disk is returned then.  ``fit_`` keeps the fitted ``TSNE`` of the last run that computed one.  ``quality_k`` (a list
+    of neighbourhood sizes, --embed_quality_k): also plot/tsne_quality.csv (k, trustworthiness, continuity, neighbors_kept as %.17g) from ``fit.quality``;
+    without it that file is neither written nor looked for."""
     FILES = ('tsne.csv', 'tsne_kl.csv')
+    QUALITY_FILE = 'tsne_quality.csv'
 
-    def __init__(self, out_path, perplexity=30.0, max_iter=1000):
+    def __init__(self, out_path, perplexity=30.0, max_iter=1000, quality_k=None):
         self.perplexity, self.max_iter = perplexity, max_iter
+        self.quality_k = [int(k) for k in quality_k] if quality_k else None
         self.out_path = osp.join(out_path, 'plot')
         os.makedirs(self.out_path, exist_ok=True)
         self.fit_ = None
@@ -1013,7 +1022,9 @@ class Tsne(object):
         overwrite = kwargs.get('overwrite', False)
         self.fit_ = None
         map_csv, kl_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (map_csv, kl_csv)) and not overwrite:
+        quality_csv = osp.join(self.out_path, self.QUALITY_FILE)
+        wanted = (map_csv, kl_csv) + ((quality_csv,) if self.quality_k else ())
+        if all(osp.exists(f) for f in wanted) and not overwrite:
             logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(map_csv))
             return pd.read_csv(kl_csv, float_precision='round_trip')
         dev = torch.device('cuda', torch.cuda.current_device())
@@ -1023,6 +1034,12 @@ class Tsne(object):
         pd.DataFrame({'x': fit.embedding_[:, 0], 'y': fit.embedding_[:, 1]}).to_csv(map_csv, index=False, float_format='%.17g')
         df = pd.DataFrame(fit.kl_history_, columns=['iteration', 'kl'])
         df.to_csv(kl_csv, index=False, float_format='%.17g')
+        if self.quality_k:
+            quality = fit.quality(self.quality_k)
+            pd.DataFrame([(k,) + quality[k] for k in sorted(quality)], columns=['k', 'trustworthiness', 'continuity', 'neighbors_kept']).to_csv(
+                quality_csv, index=False, float_format='%.17g')
+            for k in sorted(quality):
+                logger.info('t-SNE map at k: {}, trustworthiness: {:.6f}, continuity: {:.6f}, neighbors kept: {:.6f}'.format(k, *quality[k]))
         logger.info('Saved for {}!.'.format(map_csv))
         self.fit_ = fit
         return df
@@ -1097,7 +1114,7 @@ class Cluster(object):
             self.load_data()
             if getattr(self.args, 'embed', None) == 'tsne' and dist.rank() == 0:          # (an args object from before the flag: no map)
                 # one fit, on rank 0, beside whatever --cluster_method writes; it draws nothing from numpy's global stream
-                Tsne(self.out_path, self.args.tsne_perplexity, self.args.tsne_max_iter).train(self.train_data, self.valid_data)
+                Tsne(self.out_path, self.args.tsne_perplexity, self.args.tsne_max_iter, getattr(self.args, 'embed_quality_k', None)).train(self.train_data, self.valid_data)
             if self.args.cluster_method == 'dbscan':
                 if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
                     eps_range = np.arange(.5, 5.1, .5)

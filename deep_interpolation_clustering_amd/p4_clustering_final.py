@@ -48,6 +48,8 @@ take the nearest centre (``predict``) or, with --transfer knn, the vote among th
 ``--embed tsne`` (no upstream counterpart; beside any --cluster_method): one exact t-SNE fit of the training cohort on the GPU (tsne.py: --tsne_perplexity,
 --tsne_max_iter); the validation and test cohorts are PLACED on that map by ``transform`` -- every encounter at the p-weighted mean of its nearest training
 encounters' positions -- not embedded again; writes <cohort>_tsne.npy with ``encounter_id``, ``hidden`` and ``tsne`` (N, 2) f64.  Without --embed nothing changes.
+``--embed_quality_k 5 10 30`` (with --embed tsne): training_tsne_quality.csv beside training_tsne.npy (k, trustworthiness, continuity, neighbors_kept as
+%.17g; embedding_quality.py) -- the training cohort only: the placed cohorts are no fit, and a rank of queries against an index is not built.
 """
 import argparse
 import copy
@@ -116,6 +118,9 @@ def get_arguments(argv=None):
                    help='(extra) also write a two-dimensional map of every cohort (<cohort>_tsne.npy): one fit of the training cohort, the others placed on it')
     p.add_argument('--tsne_perplexity', type=float, default=30.0, help="(extra) perplexity of --embed tsne; default 30, sklearn's")
     p.add_argument('--tsne_max_iter', type=int, default=1000, help="(extra) iterations of --embed tsne; default 1000, sklearn's (250 of them exaggerated)")
+    p.add_argument('--embed_quality_k', type=int, nargs='+', default=None,
+                   help='(extra) with --embed tsne: also write trustworthiness, continuity and the share of neighbours kept of the training map at these '
+                        'neighbourhood sizes (training_tsne_quality.csv), e.g. 5 10 30')
     return p.parse_args(argv)
 
 
@@ -414,14 +419,22 @@ class Cluster(object):
     def _embed_tsne(self, cohorts, overwrite):
         """--embed tsne: one exact t-SNE fit of the training cohort (tsne.py: init 'pca', --tsne_perplexity, --tsne_max_iter); the validation and test
         cohorts are PLACED on that map by ``transform`` (every encounter at the p-weighted mean of its nearest training encounters' positions), not
-        embedded again.  Writes <cohort>_tsne.npy: ``encounter_id``, ``hidden`` and ``tsne`` (N, 2) f64, in the cohort's row order."""
+        embedded again.  Writes <cohort>_tsne.npy: ``encounter_id``, ``hidden`` and ``tsne`` (N, 2) f64, in the cohort's row order.  With --embed_quality_k
+        also training_tsne_quality.csv (k, trustworthiness, continuity, neighbors_kept) of the fitted map -- the training cohort only."""
         files = [osp.join(self.out_path, '{}_tsne.npy'.format(cohort)) for cohort, _ in cohorts]
-        if all(osp.exists(f) for f in files) and not overwrite:
+        quality_k = getattr(self.args, 'embed_quality_k', None)          # (an args object from before the flag: no table)
+        quality_csv = osp.join(self.out_path, 'training_tsne_quality.csv')
+        if all(osp.exists(f) for f in files + ([quality_csv] if quality_k else [])) and not overwrite:
             logger.info('Not Save for {}.'.format(files[0]))
             return
         logger.info('==> Generate the t-SNE map with perplexity: {}'.format(self.args.tsne_perplexity))
         model = TSNE(perplexity=self.args.tsne_perplexity, max_iter=self.args.tsne_max_iter, init='pca').fit(self.train_data['hidden'])
         logger.info('t-SNE n_iter: {}, kl: {:.6f}'.format(model.n_iter_, model.kl_divergence_))
+        if quality_k and (overwrite or not osp.exists(quality_csv)):
+            quality = model.quality([int(k) for k in quality_k])
+            pd.DataFrame([(k,) + quality[k] for k in sorted(quality)], columns=['k', 'trustworthiness', 'continuity', 'neighbors_kept']).to_csv(
+                quality_csv, index=False, float_format='%.17g')
+            logger.info('Map quality: training is done. Save to {}'.format(quality_csv))
         for (cohort, data), f in zip(cohorts, files):
             if osp.exists(f) and not overwrite:
                 logger.info('Not Save for {}.'.format(f))

@@ -292,7 +292,9 @@ class TSNE:
         if not isinstance(self.init, str) and tuple(np.shape(self.init)) != (n, 2):
             raise ValueError('init must be (n_samples, 2) = (%d, 2), got shape %s' % (n, tuple(np.shape(self.init))))
         dev = X.device if isinstance(X, torch.Tensor) and X.is_cuda else _device()
-        graph, beta = _joint(X, self.perplexity, _lists)
+        lists = kneighbors(X, n_neighbors_of(self.perplexity, n) + 1, return_device=True) if _lists is None else _lists
+        graph, beta = _joint(X, self.perplexity, lists)
+        self._raw_idx = lists[1]          # the raw self-join lists: ``quality`` takes the input-space neighbours from them
         ee = float(self.early_exaggeration)
         lr = max(n / ee / 4.0, 50.0) if self.learning_rate == 'auto' else float(self.learning_rate)
         run = _Descent(graph, self._initial(X, n, dev))
@@ -329,6 +331,16 @@ class TSNE:
         self.n_samples_fit_, self.n_features_in_ = n, d
         return self
 
+    def quality(self, ks=(5,)):
+        """``{k: (trustworthiness, continuity, neighbors_kept)}`` of the fitted map against the training points (embedding_quality.py: the map rounded to
+        f32; every k < n_samples / 2) -- the figures that compare maps across perplexities, initialisations and methods, which KL does not.  The
+        input-space neighbours come from the lists the fit (or its ``tsne_sweep``) joined, where they are wide enough: max(ks) <= int(3 perplexity + 1);
+        the result is that of ``embedding_quality(X, embedding_, ks)`` either way."""
+        if not hasattr(self, '_Y'):
+            raise RuntimeError("This TSNE instance is not fitted yet. Call 'fit' with appropriate arguments before using this estimator.")
+        from .embedding_quality import embedding_quality
+        return embedding_quality(self._X, self.embedding_, ks, _x_raw_idx=self._raw_idx)
+
     def fit_transform(self, X, y=None):
         return self.fit(X).embedding_
 
@@ -347,7 +359,8 @@ class TSNE:
 
 def tsne_sweep(X, perplexities, **kw):
     """{perplexity: fitted ``TSNE``} from ONE neighbour join, at the largest perplexity: the sorted lists of a smaller perplexity are prefixes of it, so
-    every fit has the bits of its stand-alone fit.  ``kw``: the other arguments of ``TSNE``."""
+    every fit has the bits of its stand-alone fit.  ``kw``: the other arguments of ``TSNE``.  Every fit answers ``quality(ks)`` from the same join (the
+    lists of the largest perplexity serve every map's input-space side), so the maps of a sweep can be ranked: KL cannot, P changes with the perplexity."""
     perplexities = list(perplexities)
     if not perplexities:
         raise ValueError('perplexities must name at least one perplexity')

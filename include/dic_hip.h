@@ -646,6 +646,32 @@ size_t dic_knn_neighbors_workspace(int64_t N, int64_t M, int D, int64_t candidat
 int dic_knn_neighbors(const float* X, long ldx, int64_t N, const float* Q, long ldq, int64_t M, const float* centre, int D, int k, double* dist, int32_t* idx,
                       int64_t candidate_budget, int64_t* stats, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* Neighbour RANKS without the distance matrix (csrc/dic_knn_rank.hip): where does j stand among the neighbours of i -- the counterpart of dic_knn_neighbors,
+ * which returns the neighbour at a given rank.  knn.py's neighbor_ranks and embedding_quality.py (trustworthiness, continuity) are built on it.
+ * THE DEFINITION, stated here once.  Points are f32; d2(i, l) = the f64 difference-form squared distance of csrc/dic_exactd2.h.  The order of row i is the
+ * order of dic_knn_neighbors: by the key (d2(i, l), l), ties in distance settled by the smaller index.
+ *   rank(i, j) = 1 + #{ l != i : (d2(i, l), l) < (d2(i, j), j) }   for j != i:
+ *       the 1-based position of j in row i of the self join's idx at k = N after the row's own index i is dropped (the rule t-SNE's lists follow; with
+ *       duplicates i need not come first in its own list, and a duplicate of i is a neighbour like any other).
+ *   A target j == i or j outside [0, N) (absent: write -1) has rank 0.
+ * What embedding_quality.py makes of it (Venna and Kaski 2001), X the points and Y their map, kNN_Z(i) = the k nearest OTHER points of i in space Z:
+ *   trustworthiness  T(k) = 1 - 2 / (N k (2N - 3k - 1)) * sum_i sum_{j in U_i} (rank_X(i, j) - k),  U_i = kNN_Y(i) \ kNN_X(i);  k < N / 2.
+ *   continuity       C(k): the same with the two spaces swapped -- kNN_X(i) \ kNN_Y(i), ranked on the map.
+ *   neighbours kept  mean_i |kNN_X(i) n kNN_Y(i)| / k.
+ *   MAP PRECISION: the map is f64 and this machinery f32; map-side lists and ranks are those of the map ROUNDED TO f32 (at |Y| around 50 a 4e-6 grid).
+ * Self join only.  X, ldx, centre, N, D as for dic_knn_neighbors (D <= 256, D % 4 == 0, ldx % 4 == 0, N < 2^30, 16-B aligned; centre (1, D) f32 = the mean
+ * of the points).  targets (N, m) int32 and ranks (N, m) int32, DEVICE, ranks OVERWRITTEN; 1 <= m <= 1023 (more, or D > 256: DIC_ERR_UNSUPPORTED).
+ *   dic_knn_ranks: one kernel computes the exact d2 of every target; ceil(m / 8) counting pair passes (8 targets = 16 per-row thresholds each) count the
+ *       pairs the approximate products place certainly before each target; the pairs inside a target's band -- the ones they cannot place -- are listed by
+ *       as many pair passes, group of rows by group of rows, and decided by (d2, index) in f64.  The approximate d2 never decides a rank.
+ *       candidate_budget = the bytes of list storage inside the workspace (8 per band pair and target; <= 0: the default, 384 MiB), which sizes the groups
+ *       and nothing else: the result does not depend on it.  stats (HOST, 5 int64, may be NULL): counting passes, groups, the longest row's band pairs, the
+ *       band pairs of all rows, the candidate_budget the longest row needs.  A row whose bands alone exceed the budget returns DIC_ERR_WORKSPACE with stats
+ *       filled (run again with candidate_budget >= stats[4]).  Reads list sizes back: synchronises `stream`.  Two calls give the same bits. */
+size_t dic_knn_ranks_workspace(int64_t N, int D, int m, int64_t candidate_budget);
+int dic_knn_ranks(const float* X, long ldx, const float* centre, int64_t N, int D, const int32_t* targets, int m, int32_t* ranks, int64_t candidate_budget,
+                  int64_t* stats, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 /* A TEST INSTRUMENT (csrc/dic_pairtile_probe.hip), not an operator: the approximate squared distances a_ij of the shared pair-tile loop (csrc/dic_pairtile.h),
  * which dic_dbscan_*, dic_knn_*, dic_meanshift_members and dic_kmedoids_delta_pass decide on in registers and never store, written out so that
  * tests/test_gpu_pairtile.py can hold them to the header's bound |a_ij - d^2_ij| < 2^-12 (n_i + nmax_J).  Nothing in the package calls it.
