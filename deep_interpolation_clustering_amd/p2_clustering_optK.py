@@ -86,6 +86,13 @@ plot/tsne_kl.csv (iteration, kl).  Without --embed nothing changes.  ``--embed_q
 neighbourhoods can be believed (embedding_quality.py): plot/tsne_quality.csv (k, trustworthiness, continuity, neighbors_kept as %.17g, one row per k), the
 figures that are comparable across perplexities, which kl is not.  Without that flag no such file is written.
 
+``--outlier lof`` (no upstream counterpart; beside any --cluster_method): the local outlier factor of every training encounter (lof.py: sklearn's
+LocalOutlierFactor, exact for the f32 latents) at every k of --outlier_k (default 20) from ONE neighbour join.  plot/lof.csv has one row per training
+encounter in the cohort's row order: per k ``lof_k<k>`` (the positive factor, -negative_outlier_factor_, as %.17g: about 1 inside a neighbourhood, larger
+the more isolated) and ``outlier_k<k>`` (1 where the factor lies beyond the offset of --outlier_contamination: 'auto', the default, is 1.5; a float in
+(0, 0.5] is that share of the cohort), and ``lof_max``, the largest factor over the given k (Breunig's range heuristic).  plot/lof_summary.csv has one
+row per k: k, offset, n_outliers, max_lof.  Nothing is removed from any clustering branch: that stays a join on lof.csv.  Without --outlier nothing changes.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -120,6 +127,11 @@ from .utils import logger, print_dict_byline
 from .ward import Ward as WardLinkage
 
 np.random.seed(123)        # p2_clustering_optK.py:23
+
+
+def contamination_arg(text):
+    """--outlier_contamination: 'auto' or a float (lof.py refuses one outside (0, 0.5])."""
+    return text if text == 'auto' else float(text)
 
 
 def get_arguments(argv=None):
@@ -168,6 +180,11 @@ def get_arguments(argv=None):
     p.add_argument('--embed_quality_k', type=int, nargs='+', default=None,
                    help='(extra) with --embed tsne: also write trustworthiness, continuity and the share of neighbours kept of the map at these '
                         'neighbourhood sizes (plot/tsne_quality.csv), e.g. 5 10 30')
+    p.add_argument('--outlier', default=None, choices=['lof'],
+                   help='(extra) also write the local outlier factor of every training encounter (plot/lof.csv, plot/lof_summary.csv)')
+    p.add_argument('--outlier_k', type=int, nargs='+', default=[20], help="(extra) neighbourhood sizes of --outlier lof, one join for all; default 20, sklearn's")
+    p.add_argument('--outlier_contamination', type=contamination_arg, default='auto',
+                   help="(extra) --outlier lof: 'auto' (an encounter is an outlier beyond a factor of 1.5) or the share of outliers, a float in (0, 0.5]")
     return p.parse_args(argv)
 
 
@@ -1045,6 +1062,46 @@ class Tsne(object):
         return df
 
 
+class Lof(object):
+    """--outlier lof: the local outlier factor of the training latents at every k of ``ks`` from one neighbour join (``lof.LofSweep``).  Writes
+    plot/lof.csv (per k ``lof_k<k>`` = -negative_outlier_factor_ as %.17g and ``outlier_k<k>`` = 0 / 1, then ``lof_max``; one row per training encounter in
+    the cohort's row order) and plot/lof_summary.csv (k, offset, n_outliers, max_lof) and returns the latter table.  Existing files are left alone unless
+    ``overwrite`` is set; the table on disk is returned then.  ``fit_`` keeps the ``LofSweep`` of the last run that computed one."""
+    FILES = ('lof.csv', 'lof_summary.csv')
+
+    def __init__(self, out_path, ks=(20,), contamination='auto'):
+        self.ks = sorted(set(int(k) for k in ks))
+        self.contamination = contamination
+        self.out_path = osp.join(out_path, 'plot')
+        os.makedirs(self.out_path, exist_ok=True)
+        self.fit_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        from .lof import LofSweep          # (here, not at module scope: a run without --outlier loads nothing of it)
+        overwrite = kwargs.get('overwrite', False)
+        self.fit_ = None
+        lof_csv, summary_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        if osp.exists(lof_csv) and osp.exists(summary_csv) and not overwrite:
+            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(lof_csv))
+            return pd.read_csv(summary_csv, float_precision='round_trip')
+        dev = torch.device('cuda', torch.cuda.current_device())
+        fit = LofSweep(torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev), self.ks, contamination=self.contamination)
+        columns = {}
+        for t, k in enumerate(self.ks):
+            columns['lof_k{}'.format(k)] = -fit.nof[:, t]
+            columns['outlier_k{}'.format(k)] = (fit.nof[:, t] < fit.offsets[t]).astype(np.int64)
+        columns['lof_max'] = (-fit.nof).max(axis=1)
+        pd.DataFrame(columns).to_csv(lof_csv, index=False, float_format='%.17g')
+        df = pd.DataFrame({'k': self.ks, 'offset': fit.offsets, 'n_outliers': [int(columns['outlier_k{}'.format(k)].sum()) for k in self.ks],
+                           'max_lof': [float(columns['lof_k{}'.format(k)].max()) for k in self.ks]})
+        df.to_csv(summary_csv, index=False, float_format='%.17g')
+        for row in df.itertuples(index=False):
+            logger.info('LOF at k: {}, offset: {:.6f}, outliers: {}, max factor: {:.6f}'.format(row.k, row.offset, row.n_outliers, row.max_lof))
+        logger.info('Saved for {}!.'.format(lof_csv))
+        self.fit_ = fit
+        return df
+
+
 class Consensus(object):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
@@ -1115,6 +1172,8 @@ class Cluster(object):
             if getattr(self.args, 'embed', None) == 'tsne' and dist.rank() == 0:          # (an args object from before the flag: no map)
                 # one fit, on rank 0, beside whatever --cluster_method writes; it draws nothing from numpy's global stream
                 Tsne(self.out_path, self.args.tsne_perplexity, self.args.tsne_max_iter, getattr(self.args, 'embed_quality_k', None)).train(self.train_data, self.valid_data)
+            if getattr(self.args, 'outlier', None) == 'lof' and dist.rank() == 0:          # (an args object from before the flag: no scores)
+                Lof(self.out_path, self.args.outlier_k, self.args.outlier_contamination).train(self.train_data, self.valid_data)
             if self.args.cluster_method == 'dbscan':
                 if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
                     eps_range = np.arange(.5, 5.1, .5)

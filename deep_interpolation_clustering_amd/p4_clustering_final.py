@@ -50,6 +50,11 @@ take the nearest centre (``predict``) or, with --transfer knn, the vote among th
 encounters' positions -- not embedded again; writes <cohort>_tsne.npy with ``encounter_id``, ``hidden`` and ``tsne`` (N, 2) f64.  Without --embed nothing changes.
 ``--embed_quality_k 5 10 30`` (with --embed tsne): training_tsne_quality.csv beside training_tsne.npy (k, trustworthiness, continuity, neighbors_kept as
 %.17g; embedding_quality.py) -- the training cohort only: the placed cohorts are no fit, and a rank of queries against an index is not built.
+``--outlier lof`` (no upstream counterpart; beside any --cluster_method): the local outlier factor (lof.py: sklearn's LocalOutlierFactor) at every k of
+--outlier_k (default 20).  The training cohort is FITTED once, one neighbour join for all k; the validation and test cohorts are SCORED against it as new
+encounters (sklearn's novelty ``score_samples``), one query join per cohort.  Writes <cohort>_lof.npy with ``encounter_id``, ``ks``, ``lof`` (N, nk) f64 --
+the positive factor, about 1 inside a neighbourhood -- and ``outlier`` (N, nk) bool: beyond the TRAINING fit's offset per k (--outlier_contamination:
+'auto', the default, is a factor of 1.5; a float in (0, 0.5] is that share of the training cohort).  Without --outlier nothing changes.
 """
 import argparse
 import copy
@@ -77,6 +82,11 @@ from .utils import logger, print_dict_byline
 from .ward import Ward
 
 np.random.seed(123)        # p4_clustering_final.py:24
+
+
+def contamination_arg(text):
+    """--outlier_contamination: 'auto' or a float (lof.py refuses one outside (0, 0.5])."""
+    return text if text == 'auto' else float(text)
 
 
 def get_arguments(argv=None):
@@ -121,6 +131,12 @@ def get_arguments(argv=None):
     p.add_argument('--embed_quality_k', type=int, nargs='+', default=None,
                    help='(extra) with --embed tsne: also write trustworthiness, continuity and the share of neighbours kept of the training map at these '
                         'neighbourhood sizes (training_tsne_quality.csv), e.g. 5 10 30')
+    p.add_argument('--outlier', default=None, choices=['lof'],
+                   help='(extra) also write the local outlier factor of every cohort (<cohort>_lof.npy): one fit of the training cohort, the others scored against it')
+    p.add_argument('--outlier_k', type=int, nargs='+', default=[20], help="(extra) neighbourhood sizes of --outlier lof, one join for all; default 20, sklearn's")
+    p.add_argument('--outlier_contamination', type=contamination_arg, default='auto',
+                   help="(extra) --outlier lof: 'auto' (an encounter is an outlier beyond a factor of 1.5) or the share of outliers in the training cohort, a "
+                        'float in (0, 0.5]')
     return p.parse_args(argv)
 
 
@@ -443,6 +459,26 @@ class Cluster(object):
             np.save(f, {'encounter_id': data['encounter_id'], 'hidden': data['hidden'], 'tsne': tsne})
             logger.info('Cohort map: {} is done. Save to {}'.format(cohort, f))
 
+    def _outlier_lof(self, cohorts, overwrite):
+        """--outlier lof: one fit of the training cohort at every k of --outlier_k (``lof.LofSweep``: one neighbour join); the validation and test cohorts
+        are scored against it as new encounters, one query join each.  Writes <cohort>_lof.npy: ``encounter_id``, ``ks``, ``lof`` (N, nk) f64 = the
+        positive factor and ``outlier`` (N, nk) bool = beyond the training fit's offset, in the cohort's row order."""
+        files = [osp.join(self.out_path, '{}_lof.npy'.format(cohort)) for cohort, _ in cohorts]
+        if all(osp.exists(f) for f in files) and not overwrite:
+            logger.info('Not Save for {}.'.format(files[0]))
+            return
+        from .lof import LofSweep          # (here, not at module scope: a run without --outlier loads nothing of it)
+        ks = sorted(set(int(k) for k in self.args.outlier_k))
+        logger.info('==> Generate the local outlier factors with k: {}'.format(ks))
+        model = LofSweep(np.asarray(self.train_data['hidden'], dtype=np.float32), ks, contamination=self.args.outlier_contamination)
+        for (cohort, data), f in zip(cohorts, files):
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            nof = model.nof if cohort == 'training' else model.score_samples(np.asarray(data['hidden'], dtype=np.float32))
+            np.save(f, {'encounter_id': data['encounter_id'], 'ks': np.asarray(ks, dtype=np.int64), 'lof': -nof, 'outlier': nof < model.offsets[None, :]})
+            logger.info('Cohort outlier factors: {} is done. Save to {}'.format(cohort, f))
+
     def _raw_consensus(self, cohort, data):
         """The raw consensus labels of a cohort for k = num_clusters, 0-based as generate_align_map wants them (p4:247-253): column k<num_clusters> of
         raw_consensus_result/<cohort>_consensus.csv, computed and written first where the file is missing."""
@@ -502,6 +538,8 @@ class Cluster(object):
             cohorts = list(zip(COHORTS, [self.train_data, self.valid_data, self.test_data]))
             if getattr(self.args, 'embed', None) == 'tsne':          # (an args object from before the flag: no map)
                 self._embed_tsne(cohorts, overwrite)
+            if getattr(self.args, 'outlier', None) == 'lof':          # (an args object from before the flag: no scores)
+                self._outlier_lof(cohorts, overwrite)
             if self.args.cluster_method == 'kmeans':
                 k = self.args.num_clusters
                 logger.info('==> Generate the k-means results with opt-k: {}'.format(k))

@@ -1043,6 +1043,27 @@ int dic_tsne_step(const int64_t* indptr, const int32_t* indices, const double* p
                   size_t workspace_bytes, double exaggeration, double momentum, double learning_rate, double* update, double* gains, double* Ynew,
                   double* grad, double* partials, dic_stream_t stream);
 
+/* Local outlier factor (csrc/dic_lof.hip, lof.py): sklearn 1.7.2's LocalOutlierFactor for the euclidean metric, stated here once.  All arithmetic is f64.
+ *   A fit on N rows uses k = max(1, min(n_neighbors, N - 1)).  (dist, idx) (N, k): the k nearest rows of every row sorted by (distance, index), its own index
+ *       left out (dic_knn_neighbors, self join with k + 1, the entry of the row's own index dropped, the first entry where it is not among them).
+ *       kdist[j] = dist[j, k - 1];  reach(i, s) = max(kdist[idx[i, s]], dist[i, s]);  lrd[i] = 1 / (mean_s reach(i, s) + 1e-10);
+ *       negative_outlier_factor[i] = -mean_s (lrd[idx[i, s]] / lrd[i]).
+ *   New rows (novelty): (dist, idx) (M, k) are their k nearest rows of the fitted set, nothing left out; kdist and the neighbours' lrd are the fit's, lrd_q
+ *       is formed as above, score = -mean_s (lrd[idx[q, s]] / lrd_q[q]).
+ *   Several k from one set of lists: the first k columns of a (distance, index)-ordered list are the list at k, so every k is defined on a prefix.
+ * ks (nk) int HOST, strictly ascending, 1 <= ks[t] <= ld, 1 <= nk <= 64 (more: DIC_ERR_UNSUPPORTED).  dist (M, ld) f64 and idx (M, ld) int32 row-major with
+ * row stride ld, DEVICE; the tables kdist, lrd_fit (n, nk) and lrd, lrd_rows, nof (M, nk) f64 DEVICE, column t belonging to ks[t].  1 <= M, n < 2^30.  The
+ * CONTENTS of idx are not validated: the caller guarantees 0 <= idx < n (an entry outside is clamped into the range -- no wild read, a meaningless value).
+ * Every sum runs over s = 0 .. ks[t] - 1 in that order, whatever the launch geometry and the other entries of ks: no floating-point atomics, two calls give the
+ * same bits, and column t of a call with several k has the bits of the call with ks[t] alone.  Nothing synchronises `stream`.
+ *   dic_lof_lrd: lrd[i, t] = 1 / ((sum_{s < ks[t]} max(kdist[idx[i, s], t], dist[i, s])) / ks[t] + 1e-10), OVERWRITTEN.  For the fit M = n and the lists are
+ *       the self-excluded ones.
+ *   dic_lof_scores: nof[i, t] = -(sum_{s < ks[t]} lrd_fit[idx[i, s], t]) / (ks[t] lrd_rows[i, t]), OVERWRITTEN (the fit: lrd_rows = lrd_fit). */
+int dic_lof_lrd(const double* dist, const int32_t* idx, int64_t M, int ld, const double* kdist, int64_t n, const int* ks, int nk, double* lrd,
+                dic_stream_t stream);
+int dic_lof_scores(const int32_t* idx, int64_t M, int ld, const double* lrd_fit, int64_t n, const double* lrd_rows, const int* ks, int nk, double* nof,
+                   dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
