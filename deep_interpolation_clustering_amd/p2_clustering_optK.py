@@ -106,6 +106,7 @@ import pandas as pd
 import torch
 
 from . import cluster_stats, dist
+from ._cluster_cli import METHODS, build_metrics, contamination_arg, device_latents, metric_log, metric_values, noise_summary, spell
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
 from .density_peaks import density_peaks_sweep
@@ -113,7 +114,7 @@ from .gmm import gmm_sweep
 from .gmm_full import gmm_full_sweep
 from .hdbscan import hdbscan_sizes
 from .info import COHORTS
-from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
+from .internal_eval import DunnIndex
 from .kmeans import KMeans, seed_draw_count
 from .kmedoids import kmedoids_sweep
 from .meanshift import estimate_bandwidth, mean_shift_sweep
@@ -129,14 +130,9 @@ from .ward import Ward as WardLinkage
 np.random.seed(123)        # p2_clustering_optK.py:23
 
 
-def contamination_arg(text):
-    """--outlier_contamination: 'auto' or a float (lof.py refuses one outside (0, 0.5])."""
-    return text if text == 'auto' else float(text)
-
-
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids', 'densitypeaks'])
+    p.add_argument('--cluster_method', default='kmeans', choices=METHODS)
     p.add_argument('--k_max', type=int, default=10, help='The max value of k, for k-means only.')
     p.add_argument('--select_opt_k', default=['gap_sts', 'elbow'])
     p.add_argument('--select_eps', type=str, default='k_distance_graph')
@@ -282,14 +278,51 @@ class _StreamWalker:
         self.thread.join()
 
 
-class KM(object):
-    def __init__(self, k_max, out_path, internal_metrics, n_init, gap_b, metric_sample=0):
-        self.k_max, self.n_init, self.gap_b, self.metric_sample = k_max, n_init, gap_b, metric_sample
+class _Branch(object):
+    """What the branch objects below share: the plot directory, the --internal_metrics of a labelling, and "my files exist and ``overwrite`` is not set:
+    leave them alone and return the table on disk".  Where the branches differ in that, the difference is data: ``FILES`` (what a run writes),
+    ``NAMED`` (which of them the 'Not saved for' line names), ``TABLE`` (which of them ``train`` returns) and ``ROUND_TRIP`` (how it is read back)."""
+    FILES = ()
+    NAMED = 0
+    TABLE = 0
+    ROUND_TRIP = True          # float_precision='round_trip' (repr / %.17g: exact)
+
+    def _open(self, out_path, internal_metrics=(), metric_sample=0):
         self.out_path = osp.join(out_path, 'plot')
         os.makedirs(self.out_path, exist_ok=True)
-        self.internal_metrics_names = internal_metrics
-        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
-        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self.metric_sample = metric_sample
+        self.internal_metrics_names = list(internal_metrics)
+        self.internal_metrics = build_metrics(internal_metrics)
+
+    def _paths(self):
+        return [osp.join(self.out_path, name) for name in self.FILES]
+
+    def _left_alone(self, overwrite, wanted=None, named=None):
+        """True, and logged, where every file of ``wanted`` (default: all of ``FILES``) exists and ``overwrite`` is not set."""
+        paths = self._paths()
+        if overwrite or not all(osp.exists(f) for f in (paths if wanted is None else wanted)):
+            return False
+        logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(paths[self.NAMED] if named is None else named))
+        return True
+
+    def _table_on_disk(self):
+        """The table an earlier run wrote; None where it wrote none (only Optics leaves its files alone without looking for the table)."""
+        f = self._paths()[self.TABLE]
+        if not osp.exists(f):
+            return None
+        return pd.read_csv(f, float_precision='round_trip') if self.ROUND_TRIP else pd.read_csv(f)
+
+    def _metric_values(self, Xd, labels, **kwargs):
+        return metric_values(Xd, labels, self.internal_metrics, self.metric_sample, **kwargs)
+
+    def _metric_log(self, vals):
+        return metric_log(self.internal_metrics_names, vals)
+
+
+class KM(_Branch):
+    def __init__(self, k_max, out_path, internal_metrics, n_init, gap_b, metric_sample=0):
+        self.k_max, self.n_init, self.gap_b = k_max, n_init, gap_b
+        self._open(out_path, internal_metrics, metric_sample)
 
     # -- inertia definitions of the gap statistic (p2:334-351): one tiled pair pass on the device, nothing n x n
     def compute_inertia_v1(self, a, X, stats=None):
@@ -345,7 +378,7 @@ class KM(object):
             nxt = stage(next(it, None))
             yield ki, i, refd, state
 
-    def _fit_problems(self, walker, table, ks, n_references, Xd, data, lo, rng_, dev, inertia, need_minmax):
+    def _fit_problems(self, walker, table, ks, n_references, Xd, lo, rng_, dev, inertia, need_minmax):
         """The fits of this rank's (K, reference set) problems, in stream order (see compute_gap_internal_metric)."""
         for ki, i, refd, state in self._staged(walker, dev, lo, rng_):
             k = ks[ki]
@@ -361,12 +394,7 @@ class KM(object):
             assignments = km.fit_predict(Xd)
             stats = cluster_stats.pair_stats(Xd, assignments, need_min=need_minmax, need_max=need_minmax)
             table[ki, n_references] = np.log(inertia(assignments, Xd, stats))      # the same pair pass feeds the gap term and every index
-            if self.metric_sample and self.metric_sample < len(data):
-                pick = np.random.RandomState(0).choice(len(data), self.metric_sample, replace=False)
-                vals = [m(Xd[torch.as_tensor(pick, device=dev)], assignments[pick]) for m in self.internal_metrics]
-            else:
-                vals = [m(Xd, assignments, stats=stats) for m in self.internal_metrics]
-            table[ki, n_references + 1:] = vals
+            table[ki, n_references + 1:] = self._metric_values(Xd, assignments, stats=stats)
         return table
 
     def compute_gap_internal_metric(self, data, k_max=5, n_references=5, version=1):
@@ -393,7 +421,7 @@ class KM(object):
         need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
         walker = _StreamWalker(data.shape, ks, n_references, KMeans(n_init=self.n_init)._resolve_n_init(False), rank, world)
         try:
-            table = self._fit_problems(walker, table, ks, n_references, Xd, data, lo, rng_, dev, inertia, need_minmax)
+            table = self._fit_problems(walker, table, ks, n_references, Xd, lo, rng_, dev, inertia, need_minmax)
         finally:
             walker.close()
         if world > 1 or dist.is_sharded():
@@ -410,7 +438,7 @@ class KM(object):
             gap = ref_mean - act
             vals = list(table[ki, n_references + 1:])
             logger.info('k: {}, gap: {:.4f}, ref: {:.4f}, act: {:.4f}, ref_s: {:.4f} '.format(k, gap, ref_mean, act, ref_s)
-                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+                        + self._metric_log(vals))
             rows.append([k, gap, ref_mean, act, ref_s] + vals)
         return pd.DataFrame(rows, columns=['k', 'gap', 'ref', 'act', 'ref_s'] + list(self.internal_metrics_names))
 
@@ -434,7 +462,7 @@ class KM(object):
         return out
 
 
-class Dbscan(object):
+class Dbscan(_Branch):
     """Dbscan.train (p2:90-168): one DBSCAN per eps of ``eps_range`` on the training latents (one counting pass for all of them), logged as upstream logs
     them; returns (and writes to plot/dbscan_eps.csv) the per-eps table.  ``select_eps == 'k_distance_graph'`` (p2:102-120) first writes the
     (min_samples - 1)-NN distance curve (plot/k_distance.csv: sample, dist) and its elbow (plot/k_distance_elbow.csv: k, elbow_x, elbow_y) and keeps them
@@ -444,16 +472,14 @@ class Dbscan(object):
     def __init__(self, eps_range, min_samples, out_path):
         self.eps_range = eps_range
         self.min_sample = min_samples
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
+        self._open(out_path)
         self.k_distance_ = None
 
     def k_distance(self, Xd, overwrite=False):
         """p2:102-120 on the device copy of the latents: the k-distance table, its elbow, the log line."""
         k = self.min_sample - 1
         csv = osp.join(self.out_path, 'k_distance.csv')
-        if osp.exists(csv) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(csv))
+        if self._left_alone(overwrite, [csv], csv):          # (dbscan_eps.csv itself is written by every run)
             return None
         graph = k_distance_graph(Xd, k)
         sorted_dist = graph['sorted_dist']
@@ -465,30 +491,14 @@ class Dbscan(object):
 
     def train(self, train_data, valid_data, select_eps, **kwargs):
         overwrite = kwargs.get('overwrite', False)
-        train_feat = train_data['hidden']
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_feat, dtype=torch.float32, device=dev)
+        Xd = device_latents(train_data)
         if select_eps == 'k_distance_graph':
             self.k_distance_ = self.k_distance(Xd, overwrite)
         fits = dbscan_sweep(Xd, self.eps_range, self.min_sample)
         rows = []
         for eps, (labels, core) in zip(self.eps_range, fits):
             logger.info('\nRunning eps: {}'.format(eps))
-            logger.info('core_sample: {}'.format(len(core)))
-            n_clusters_ = len(set(labels)) - (1 if -1 in labels else 0)
-            n_noise_ = int(np.sum(labels == -1))
-            logger.info('Estimated number of clusters: %d' % n_clusters_)
-            logger.info('Estimated number of noise points: %d' % n_noise_)
-            sil = sil_dn = float('nan')
-            if n_clusters_ == 1:
-                logger.info('Skip the Silhouette Coefficient calculation.')
-            elif n_clusters_ > 1:
-                keep = labels != -1
-                sil = cluster_stats.silhouette_score(Xd, labels)
-                sil_dn = cluster_stats.silhouette_score(Xd[torch.as_tensor(keep, device=dev)], labels[keep])
-                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(labels), sil))
-                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(int(keep.sum()), sil_dn))
-            rows.append([float(eps), len(core), n_clusters_, n_noise_, sil, sil_dn])
+            rows.append([float(eps), len(core)] + list(noise_summary(Xd, labels, len(core))))
         df = pd.DataFrame(rows, columns=self.COLUMNS)
         df.to_csv(osp.join(self.out_path, 'dbscan_eps.csv'), index=False)
         return df
@@ -499,7 +509,7 @@ def snn_default_eps(k):
     return sorted({min(k, max(1, int(round(k * t / 10.0)))) for t in range(2, 9)})
 
 
-class Snn(object):
+class Snn(_Branch):
     """One shared-neighbour graph of the training latents (``snn.snn_sweep``: ``k`` neighbours) labelled once per eps of ``eps_values`` at ``min_samples``,
     logged as Dbscan.train logs its fits.  Writes plot/snn_eps.csv (``COLUMNS``: Dbscan's, the silhouettes computed the same way, plus k and min_samples),
     plot/snn_similarity_hist.csv (similarity 0..k, pairs: the list entries at that similarity, the self entries and the pairs that are not mutual at 0) and
@@ -510,39 +520,22 @@ class Snn(object):
 
     def __init__(self, k, eps_values, min_samples, out_path):
         self.k, self.eps_values, self.min_sample = int(k), [int(e) for e in eps_values], int(min_samples)
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
+        self._open(out_path)
         self.labels_ = self.stats_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.labels_ = self.stats_ = None
-        eps_csv, hist_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (eps_csv, hist_csv, labels_csv)) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(eps_csv))
-            return pd.read_csv(eps_csv, float_precision='round_trip')          # (repr: exact)
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        eps_csv, hist_csv, labels_csv = self._paths()
+        Xd = device_latents(train_data)
         stats = {}
         fits = snn_sweep(Xd, self.k, self.eps_values, self.min_sample, stats=stats)
         rows = []
         for eps, (labels, core, _) in zip(self.eps_values, fits):
             logger.info('\nRunning eps: {} (shared neighbours of {}), min_samples: {}'.format(eps, self.k, self.min_sample))
-            logger.info('core_sample: {}'.format(len(core)))
-            n_clusters_ = len(set(labels.tolist())) - (1 if -1 in labels else 0)
-            n_noise_ = int(np.sum(labels == -1))
-            logger.info('Estimated number of clusters: %d' % n_clusters_)
-            logger.info('Estimated number of noise points: %d' % n_noise_)
-            sil = sil_dn = float('nan')
-            if n_clusters_ == 1:
-                logger.info('Skip the Silhouette Coefficient calculation.')
-            elif n_clusters_ > 1:
-                keep = labels != -1
-                sil = cluster_stats.silhouette_score(Xd, labels)
-                sil_dn = cluster_stats.silhouette_score(Xd[torch.as_tensor(keep, device=dev)], labels[keep])
-                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(labels), sil))
-                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(int(keep.sum()), sil_dn))
-            rows.append([eps, len(core), n_clusters_, n_noise_, sil, sil_dn, self.k, self.min_sample])
+            rows.append([eps, len(core)] + list(noise_summary(Xd, labels, len(core))) + [self.k, self.min_sample])
         df = pd.DataFrame(rows, columns=self.COLUMNS)
         df.to_csv(eps_csv, index=False)
         pd.DataFrame({'similarity': np.arange(self.k + 1), 'pairs': stats['similarity_hist']}).to_csv(hist_csv, index=False)
@@ -552,33 +545,31 @@ class Snn(object):
         return df
 
 
-class Optics(object):
+class Optics(_Branch):
     """Optics.train (p2:171-223): one OPTICS fit of the training latents -- ``cluster_method`` 'xi' (xi = .05, min_cluster_size = min_samples) or 'dbscan'
     (eps = max_eps = inf) -- logged as upstream logs it; returns (and writes to plot/optics_<cluster_method>.csv) the one-row summary, and writes the data
     of upstream's reachability plot to plot/reachability_<cluster_method>.csv, every point included.  An existing reachability file is left alone unless
     ``overwrite`` is set, as upstream leaves its plot; the summary on disk is returned then.  The fit runs on the latents, not on the rows of their distance
     matrix (module docstring).  ``fit_`` keeps the fitted ``OPTICS`` of the last run that computed one."""
     COLUMNS = ['min_samples', 'n_clusters', 'n_noise']
+    TABLE, ROUND_TRIP = 1, False
 
     def __init__(self, min_samples, cluster_method, out_path):
         if cluster_method not in ('xi', 'dbscan'):
             raise ValueError("cluster_method must be 'xi' or 'dbscan', got %r" % (cluster_method,))
         self.min_sample = min_samples
         self.cluster_method = cluster_method
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
+        self.FILES = ('reachability_{}.csv'.format(cluster_method), 'optics_{}.csv'.format(cluster_method))
+        self._open(out_path)
         self.fit_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fit_ = None
-        plot_csv = osp.join(self.out_path, 'reachability_{}.csv'.format(self.cluster_method))
-        summary_csv = osp.join(self.out_path, 'optics_{}.csv'.format(self.cluster_method))
-        if osp.exists(plot_csv) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(plot_csv))
-            return pd.read_csv(summary_csv) if osp.exists(summary_csv) else None
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        plot_csv, summary_csv = self._paths()
+        if self._left_alone(overwrite, [plot_csv]):          # (the reachability file alone, as upstream looks at its plot alone)
+            return self._table_on_disk()
+        Xd = device_latents(train_data)
         if self.cluster_method == 'xi':
             optics = OPTICS(min_samples=self.min_sample, cluster_method='xi', xi=.05, min_cluster_size=self.min_sample)
         else:
@@ -598,7 +589,7 @@ class Optics(object):
         return df
 
 
-class Hdbscan(object):
+class Hdbscan(_Branch):
     """One HDBSCAN tree of the training latents (min_samples as given) and one extraction per ``min_cluster_sizes`` entry, logged as Dbscan.train logs its
     fits.  Writes plot/hdbscan_mst.csv (x, sample, source, dist: every step of Prim's walk, %.17g), plot/hdbscan_sizes.csv (``COLUMNS``; the silhouettes as
     the DBSCAN branch computes them, empty below 2 clusters) and plot/hdbscan_labels.csv (one column mcs<size> per size), and returns the per-size table.
@@ -606,45 +597,29 @@ class Hdbscan(object):
     that computed one, ``labels_`` its labels per size."""
     COLUMNS = ['min_cluster_size', 'n_clusters', 'n_noise', 'silhouette', 'denoise_silhouette']
     FILES = ('hdbscan_mst.csv', 'hdbscan_sizes.csv', 'hdbscan_labels.csv')
+    TABLE, ROUND_TRIP = 1, False
 
     def __init__(self, min_samples, min_cluster_sizes, out_path):
         self.min_sample = min_samples
         self.min_cluster_sizes = [int(m) for m in min_cluster_sizes]
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
+        self._open(out_path)
         self.fit_ = self.labels_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fit_ = self.labels_ = None
-        mst_csv, sizes_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (mst_csv, sizes_csv, labels_csv)) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(mst_csv))
-            return pd.read_csv(sizes_csv)
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        mst_csv, sizes_csv, labels_csv = self._paths()
+        Xd = device_latents(train_data)
         fit, found = hdbscan_sizes(Xd, self.min_sample, self.min_cluster_sizes)
         order = fit.ordering_
         pd.DataFrame({'x': np.arange(len(order)), 'sample': order, 'source': fit.predecessor_[order], 'dist': fit.reachability_[order]}).to_csv(
             mst_csv, index=False, float_format='%.17g')
         rows = []
         for mcs in self.min_cluster_sizes:
-            labels = found[mcs][0]
-            n_clusters_ = len(set(labels.tolist())) - (1 if -1 in labels else 0)
-            n_noise_ = int(np.sum(labels == -1))
             logger.info('\nRunning min_cluster_size: {}'.format(mcs))
-            logger.info('Estimated number of clusters: %d' % n_clusters_)
-            logger.info('Estimated number of noise points: %d' % n_noise_)
-            sil = sil_dn = float('nan')
-            if n_clusters_ == 1:
-                logger.info('Skip the Silhouette Coefficient calculation.')
-            elif n_clusters_ > 1:
-                keep = labels != -1
-                sil = cluster_stats.silhouette_score(Xd, labels)
-                sil_dn = cluster_stats.silhouette_score(Xd[torch.as_tensor(keep, device=dev)], labels[keep])
-                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(labels), sil))
-                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(int(keep.sum()), sil_dn))
-            rows.append([mcs, n_clusters_, n_noise_, sil, sil_dn])
+            rows.append([mcs] + list(noise_summary(Xd, found[mcs][0])))
         df = pd.DataFrame(rows, columns=self.COLUMNS)
         df.to_csv(sizes_csv, index=False)
         pd.DataFrame({'mcs{}'.format(m): found[m][0] for m in self.min_cluster_sizes}).to_csv(labels_csv, index=False)
@@ -653,7 +628,7 @@ class Hdbscan(object):
         return df
 
 
-class Ward(object):
+class Ward(_Branch):
     """One Ward tree of the training latents (``ward.Ward``), cut at K = 2..``k_max``.  Per K: the labels, the height of the merge that takes K clusters to
     K - 1, the mean distance to the nearest centre on the training and the validation latents (the elbow's distortion) and the ``internal_metrics`` as
     ``KM`` computes them -- one shared pair pass per K, ``metric_sample`` honoured -- logged per K as ``KM`` logs.  Writes plot/ward_linkage.csv (Z: left,
@@ -661,29 +636,21 @@ class Ward(object):
     0-based) and returns the per-K table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.  ``fit_`` keeps the
     fitted ``ward.Ward`` of the last run that computed one."""
     FILES = ('ward_linkage.csv', 'ward_k.csv', 'ward_labels.csv')
+    TABLE = 1
 
     def __init__(self, k_max, out_path, internal_metrics, metric_sample=0):
         self.ks = list(range(2, k_max + 1))
-        self.metric_sample = metric_sample
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
-        self.internal_metrics_names = list(internal_metrics)
-        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
-        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self._open(out_path, internal_metrics, metric_sample)
         self.fit_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fit_ = None
-        linkage_csv, k_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (linkage_csv, k_csv, labels_csv)) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(linkage_csv))
-            return pd.read_csv(k_csv, float_precision='round_trip')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
-        Vd = torch.as_tensor(valid_data['hidden'], dtype=torch.float32, device=dev)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        linkage_csv, k_csv, labels_csv = self._paths()
+        Xd, Vd = device_latents(train_data), device_latents(valid_data)
         fit = WardLinkage(ks=self.ks).fit(Xd)
-        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
         rows = []
         for k in self.ks:
             logger.info('Running K: {}'.format(k))
@@ -691,14 +658,8 @@ class Ward(object):
             centers = fit.cluster_centers_by_k_[k]
             train_d = float(fit.nearest_distance(Xd, centers).mean())
             valid_d = float(fit.nearest_distance(Vd, centers).mean())
-            if self.metric_sample and self.metric_sample < len(labels):
-                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
-                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
-            else:
-                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
-                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
-            logger.info('k: {}, height: {:.4f}, train: {:.4f}, valid: {:.4f} '.format(k, fit.heights_by_k_[k], train_d, valid_d)
-                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+            vals = self._metric_values(Xd, labels)
+            logger.info('k: {}, height: {:.4f}, train: {:.4f}, valid: {:.4f} '.format(k, fit.heights_by_k_[k], train_d, valid_d) + self._metric_log(vals))
             rows.append([k, fit.heights_by_k_[k], train_d, valid_d] + vals)
         df = pd.DataFrame(rows, columns=['k', 'height', 'train_distortion', 'valid_distortion'] + self.internal_metrics_names)
         pd.DataFrame(fit.linkage_, columns=['left', 'right', 'height', 'size']).to_csv(linkage_csv, index=False, float_format='%.17g')
@@ -709,7 +670,7 @@ class Ward(object):
         return df
 
 
-class Kmedoids(object):
+class Kmedoids(_Branch):
     """k-medoids (PAM) of the training latents for K = 2..``k_max`` (``kmedoids.kmedoids_sweep``: the planes prepared once, one BUILD of ``k_max`` whose
     prefixes start every K, SWAP per K).  Per K: TD (``inertia``), the SWAP searches, the convergence flag and the ``internal_metrics`` of the labels as the
     Ward branch computes them -- one shared pair pass per K, ``metric_sample`` honoured -- logged per K as ``KM`` logs.  Writes plot/kmedoids_k.csv,
@@ -722,39 +683,24 @@ class Kmedoids(object):
 
     def __init__(self, k_max, out_path, internal_metrics, metric_sample=0):
         self.ks = list(range(2, k_max + 1))
-        self.metric_sample = metric_sample
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
-        self.internal_metrics_names = list(internal_metrics)
-        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
-        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self._open(out_path, internal_metrics, metric_sample)
         self.fits_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fits_ = None
-        k_csv, labels_csv, medoids_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (k_csv, labels_csv, medoids_csv)) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(k_csv))
-            return pd.read_csv(k_csv, float_precision='round_trip')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        k_csv, labels_csv, medoids_csv = self._paths()
+        Xd = device_latents(train_data)
         fits = kmedoids_sweep(Xd, self.ks)
         ids = train_data.get('encounter_id') if hasattr(train_data, 'get') else None
-        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
         rows, medoid_rows = [], []
         for k in self.ks:
             logger.info('Running K: {}'.format(k))
             fit = fits[k]
-            labels = fit.labels_
-            if self.metric_sample and self.metric_sample < len(labels):
-                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
-                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
-            else:
-                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
-                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
-            logger.info('k: {}, inertia: {:.4f}, n_iter: {}, converged: {} '.format(k, fit.inertia_, fit.n_iter_, fit.converged_)
-                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+            vals = self._metric_values(Xd, fit.labels_)
+            logger.info('k: {}, inertia: {:.4f}, n_iter: {}, converged: {} '.format(k, fit.inertia_, fit.n_iter_, fit.converged_) + self._metric_log(vals))
             rows.append([k, fit.inertia_, fit.n_iter_, int(fit.converged_)] + vals)
             for slot, at in enumerate(fit.medoid_indices_):
                 medoid_rows.append([k, slot, int(at), ids[int(at)] if ids is not None else ''])
@@ -767,7 +713,7 @@ class Kmedoids(object):
         return df
 
 
-class Densitypeaks(object):
+class Densitypeaks(_Branch):
     """Density peaks of the training latents (``density_peaks.density_peaks_sweep``: ONE device computation of rho, delta and parent, one cut per K = 2..
     ``k_max`` on the host).  Writes plot/densitypeaks_decision.csv (index, rho, delta, gamma, parent: the decision graph, every point), plot/densitypeaks_k.csv
     (k, gamma_gap, sizes -- the cluster sizes without the halo, joined by blanks --, n_halo and the ``internal_metrics`` of the labels without the halo, as the
@@ -777,44 +723,32 @@ class Densitypeaks(object):
     FILES = ('densitypeaks_decision.csv', 'densitypeaks_k.csv', 'densitypeaks_labels.csv')
     COLUMNS = ['k', 'gamma_gap', 'sizes', 'n_halo']
     DECISION_COLUMNS = ['index', 'rho', 'delta', 'gamma', 'parent']
+    NAMED = TABLE = 1
 
     def __init__(self, k_max, out_path, internal_metrics, density='cutoff', percent=2.0, dc=None, halo=False, metric_sample=0):
         self.ks = list(range(2, k_max + 1))
         self.kw = dict(density=density, percent=percent, dc='auto' if dc is None else dc, halo=bool(halo))
-        self.metric_sample = metric_sample
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
-        self.internal_metrics_names = list(internal_metrics)
-        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
-        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self._open(out_path, internal_metrics, metric_sample)
         self.fits_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fits_ = None
-        decision_csv, k_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (decision_csv, k_csv, labels_csv)) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(k_csv))
-            return pd.read_csv(k_csv, float_precision='round_trip')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        decision_csv, k_csv, labels_csv = self._paths()
+        Xd = device_latents(train_data)
         fits = density_peaks_sweep(Xd, self.ks, **self.kw)
         first = fits[self.ks[0]]
-        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
         rows = []
         for k in self.ks:
             logger.info('Running K: {}'.format(k))
             fit = fits[k]
             labels = fit.core_labels_
-            if self.metric_sample and self.metric_sample < len(labels):
-                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
-                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
-            else:
-                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
-                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
+            vals = self._metric_values(Xd, labels)
             sizes = np.bincount(labels, minlength=k)
             logger.info('k: {}, gamma gap: {:.4f}, sizes: {}, halo: {} '.format(k, fit.gamma_gap_, sizes.tolist(), int(fit.halo_.sum()))
-                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+                        + self._metric_log(vals))
             rows.append([k, fit.gamma_gap_, ' '.join(str(int(v)) for v in sizes), int(fit.halo_.sum())] + vals)
         df = pd.DataFrame(rows, columns=self.COLUMNS + self.internal_metrics_names)
         pd.DataFrame({'index': np.arange(len(first.rho_)), 'rho': first.rho_, 'delta': first.delta_, 'gamma': first.gamma_,
@@ -826,7 +760,7 @@ class Densitypeaks(object):
         return df
 
 
-class Gmm(object):
+class Gmm(_Branch):
     """Gaussian mixtures of the training latents (``gmm.gmm_sweep``) for K = 2..``k_max``, ``n_init`` restarts each.  Per K: the lower bound, BIC and AIC on the
     training latents, the iterations and whether the winning restart converged, the mean log-likelihood of the validation cohort under the training model, and
     the ``internal_metrics`` of the hard labels as ``KM`` computes them -- one shared pair pass per K, ``metric_sample`` honoured -- logged per K as ``KM``
@@ -838,44 +772,28 @@ class Gmm(object):
     def __init__(self, k_max, out_path, internal_metrics, n_init=1, covariance_type='diag', metric_sample=0):
         self.ks = list(range(2, k_max + 1))
         self.n_init, self.covariance_type = n_init, covariance_type
-        self.metric_sample = metric_sample
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
-        self.internal_metrics_names = list(internal_metrics)
-        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
-        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self._open(out_path, internal_metrics, metric_sample)
         self.fits_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fits_ = None
-        k_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (k_csv, labels_csv)) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(k_csv))
-            return pd.read_csv(k_csv, float_precision='round_trip')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
-        Vd = torch.as_tensor(valid_data['hidden'], dtype=torch.float32, device=dev)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        k_csv, labels_csv = self._paths()
+        Xd, Vd = device_latents(train_data), device_latents(valid_data)
         sweep = gmm_full_sweep if self.covariance_type in ('full', 'tied') else gmm_sweep
         fits = sweep(Xd, self.ks, covariance_type=self.covariance_type, n_init=self.n_init)
-        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
         rows = []
         for k in self.ks:
             logger.info('Running K: {}'.format(k))
             fit = fits[k]
             labels = np.unique(fit.labels_, return_inverse=True)[1].astype(np.int64)          # (a component without a row of its own is skipped by the indices)
             bic, aic, valid = float(fit.bic(Xd)), float(fit.aic(Xd)), float(fit.score(Vd))
-            if labels.max() < 1:          # (the indices need two clusters)
-                vals = [float('nan')] * len(self.internal_metrics)
-            elif self.metric_sample and self.metric_sample < len(labels):
-                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
-                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
-            else:
-                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
-                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
+            vals = self._metric_values(Xd, labels, nan_below_two=True)
             logger.info('k: {}, lower_bound: {:.4f}, bic: {:.1f}, aic: {:.1f}, n_iter: {}, valid: {:.4f} '.format(k, fit.lower_bound_, bic, aic, fit.n_iter_,
                                                                                                                 valid)
-                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+                        + self._metric_log(vals))
             rows.append([k, fit.lower_bound_, bic, aic, fit.n_iter_, int(fit.converged_), valid] + vals)
         df = pd.DataFrame(rows, columns=['k', 'lower_bound', 'bic', 'aic', 'n_iter', 'converged', 'valid_score'] + self.internal_metrics_names)
         df.to_csv(k_csv, index=False, float_format='%.17g')
@@ -885,7 +803,7 @@ class Gmm(object):
         return df
 
 
-class Meanshift(object):
+class Meanshift(_Branch):
     """Mean shift of the training latents (``meanshift.mean_shift_sweep``), one fit per bandwidth: the given ``bandwidths``, or ``estimate_bandwidth`` of the
     training latents at every quantile of ``quantiles``.  Per bandwidth: the clusters found, the orphans (``cluster_all`` off), the largest and the smallest
     cluster, the iterations, the validation cohort's mean distance to its nearest centre (``predict``) and the ``internal_metrics`` of the labels as ``KM``
@@ -899,31 +817,22 @@ class Meanshift(object):
     def __init__(self, out_path, internal_metrics, quantiles=(0.1, 0.2, 0.3), bandwidths=None, bin_seeding=False, cluster_all=True, metric_sample=0):
         self.quantiles, self.bandwidths = list(quantiles), None if bandwidths is None else [float(b) for b in bandwidths]
         self.bin_seeding, self.cluster_all = bool(bin_seeding), bool(cluster_all)
-        self.metric_sample = metric_sample
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
-        self.internal_metrics_names = list(internal_metrics)
-        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
-        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self._open(out_path, internal_metrics, metric_sample)
         self.fits_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fits_ = None
-        bw_csv, labels_csv, centers_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (bw_csv, labels_csv, centers_csv)) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(bw_csv))
-            return pd.read_csv(bw_csv, float_precision='round_trip')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
-        Vd = torch.as_tensor(valid_data['hidden'], dtype=torch.float32, device=dev)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        bw_csv, labels_csv, centers_csv = self._paths()
+        Xd, Vd = device_latents(train_data), device_latents(valid_data)
         if self.bandwidths is not None:
             plan = [(float('nan'), b) for b in self.bandwidths]
         else:
             plan = [(q, estimate_bandwidth(Xd, q)) for q in self.quantiles]
         by_bw = mean_shift_sweep(Xd, sorted(set(b for _, b in plan)), bin_seeding=self.bin_seeding, cluster_all=self.cluster_all)
         fits = [by_bw[b] for _, b in plan]
-        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
         rows = []
         for (q, b), fit in zip(plan, fits):
             logger.info('Running bandwidth: {:.6g} (quantile {})'.format(b, q))
@@ -932,18 +841,11 @@ class Meanshift(object):
             cv = fit.cluster_centers_[fit.predict(Vd)]
             valid_d = float(np.sqrt(((np.asarray(valid_data['hidden'], dtype=np.float64) - cv) ** 2).sum(axis=1)).mean())
             labels = np.unique(fit.labels_[keep], return_inverse=True)[1].astype(np.int64)
-            Xk = Xd if keep.all() else Xd[torch.as_tensor(keep, device=dev)]
-            if labels.size == 0 or labels.max() < 1:          # (the indices need two clusters)
-                vals = [float('nan')] * len(self.internal_metrics)
-            elif self.metric_sample and self.metric_sample < len(labels):
-                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
-                vals = [m(Xk[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
-            else:
-                stats = cluster_stats.pair_stats(Xk, labels, need_min=need_minmax, need_max=need_minmax)
-                vals = [m(Xk, labels, stats=stats) for m in self.internal_metrics]
+            Xk = Xd if keep.all() else Xd[torch.as_tensor(keep, device=Xd.device)]
+            vals = self._metric_values(Xk, labels, nan_below_two=True)          # (the subsample is drawn from the points that are no orphans)
             row = [q, b, len(fit.cluster_centers_), int((~keep).sum()), int(sizes.max()), int(sizes.min()), fit.n_iter_, valid_d]
             logger.info('bandwidth: {:.6g}, clusters: {}, orphans: {}, largest: {}, smallest: {}, n_iter: {}, valid: {:.4f} '.format(*row[1:])
-                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+                        + self._metric_log(vals))
             rows.append(row + vals)
         df = pd.DataFrame(rows, columns=self.COLUMNS + self.internal_metrics_names)
         df.to_csv(bw_csv, index=False, float_format='%.17g')
@@ -957,7 +859,7 @@ class Meanshift(object):
         return df
 
 
-class Spectral(object):
+class Spectral(_Branch):
     """One spectral decomposition of the training latents (``spectral.spectral_sweep``: ``k`` neighbours, k_max + 1 eigenpairs) labelled for K = 2..``k_max``
     from the first K eigenvectors.  Per K: the eigengap theta_K - theta_(K+1), the solver's iterations and whether it converged, the number of connected
     components and the ``internal_metrics`` of the labels on the latents as ``KM`` computes them -- one shared pair pass per K, ``metric_sample`` honoured.
@@ -965,6 +867,7 @@ class Spectral(object):
     plot/spectral_labels.csv (columns k2..k<k_max>, 0-based) and returns the per-K table.  Existing files are left alone unless ``overwrite`` is set; the
     table on disk is returned then.  ``fit_`` keeps the fitted ``spectral.SpectralClustering`` of the last run that computed one."""
     FILES = ('spectral_eigenvalues.csv', 'spectral_k.csv', 'spectral_labels.csv')
+    NAMED = TABLE = 1
 
     def __init__(self, k_max, out_path, internal_metrics, k=10, assign_labels='kmeans', metric_sample=0):
         if not 2 <= k_max <= MAX_CLUSTERS - 1:
@@ -972,42 +875,27 @@ class Spectral(object):
                              '{} is the compiled limit), got {}'.format(MAX_CLUSTERS - 1, MAX_CLUSTERS, k_max))
         self.ks = list(range(2, k_max + 1))
         self.k, self.assign_labels = k, assign_labels
-        self.metric_sample = metric_sample
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
-        self.internal_metrics_names = list(internal_metrics)
-        table = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
-        self.internal_metrics = [table[n]() for n in internal_metrics]
+        self._open(out_path, internal_metrics, metric_sample)
         self.fit_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fit_ = None
-        eig_csv, k_csv, labels_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if all(osp.exists(f) for f in (eig_csv, k_csv, labels_csv)) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(k_csv))
-            return pd.read_csv(k_csv, float_precision='round_trip')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        eig_csv, k_csv, labels_csv = self._paths()
+        Xd = device_latents(train_data)
         fit = spectral_sweep(Xd, self.ks, n_neighbors=self.k, assign_labels=self.assign_labels, random_state=0, n_components=self.ks[-1] + 1,
                              return_fit=True)
         theta = fit.eigenvalues_
         gaps = np.append(theta[:-1] - theta[1:], np.nan)
-        need_minmax = any(isinstance(m, DunnIndex) for m in self.internal_metrics)
         rows = []
         for k in self.ks:
             logger.info('Running K: {}'.format(k))
             labels = np.unique(fit.labels_by_k_[k], return_inverse=True)[1].astype(np.int64)          # (an empty cluster is skipped by the indices)
-            if labels.max() < 1:          # (the indices need two clusters)
-                vals = [float('nan')] * len(self.internal_metrics)
-            elif self.metric_sample and self.metric_sample < len(labels):
-                pick = np.random.RandomState(0).choice(len(labels), self.metric_sample, replace=False)
-                vals = [m(Xd[torch.as_tensor(pick, device=dev)], labels[pick]) for m in self.internal_metrics]
-            else:
-                stats = cluster_stats.pair_stats(Xd, labels, need_min=need_minmax, need_max=need_minmax)
-                vals = [m(Xd, labels, stats=stats) for m in self.internal_metrics]
+            vals = self._metric_values(Xd, labels, nan_below_two=True)
             logger.info('k: {}, eigengap: {:.6f}, n_iter: {}, components: {} '.format(k, gaps[k - 1], fit.n_iter_, fit.n_connected_components_)
-                        + ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(self.internal_metrics_names, vals)))
+                        + self._metric_log(vals))
             rows.append([k, gaps[k - 1], fit.n_iter_, int(fit.converged_), fit.n_connected_components_] + vals)
         df = pd.DataFrame(rows, columns=['k', 'eigengap', 'n_iter', 'converged', 'n_connected_components'] + self.internal_metrics_names)
         pd.DataFrame({'index': np.arange(1, len(theta) + 1), 'eigenvalue': theta, 'eigengap': gaps}).to_csv(eig_csv, index=False, float_format='%.17g')
@@ -1018,7 +906,7 @@ class Spectral(object):
         return df
 
 
-class Tsne(object):
+class Tsne(_Branch):
     """--embed tsne: one exact t-SNE fit of the training latents (``tsne.TSNE``: init 'pca', ``perplexity``, ``max_iter`` iterations).  Writes plot/tsne.csv
     (x, y as %.17g, one row per training encounter in the cohort's row order -- the order of every plot/*_labels.csv) and plot/tsne_kl.csv (iteration, kl:
     the error at every check, every 50 iterations, and at the last iteration) and returns the latter table.  Existing files are left alone unless
@@ -1027,26 +915,22 @@ class Tsne(object):
     without it that file is neither written nor looked for."""
     FILES = ('tsne.csv', 'tsne_kl.csv')
     QUALITY_FILE = 'tsne_quality.csv'
+    TABLE = 1
 
     def __init__(self, out_path, perplexity=30.0, max_iter=1000, quality_k=None):
         self.perplexity, self.max_iter = perplexity, max_iter
         self.quality_k = [int(k) for k in quality_k] if quality_k else None
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
+        self._open(out_path)
         self.fit_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fit_ = None
-        map_csv, kl_csv = (osp.join(self.out_path, name) for name in self.FILES)
+        map_csv, kl_csv = self._paths()
         quality_csv = osp.join(self.out_path, self.QUALITY_FILE)
-        wanted = (map_csv, kl_csv) + ((quality_csv,) if self.quality_k else ())
-        if all(osp.exists(f) for f in wanted) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(map_csv))
-            return pd.read_csv(kl_csv, float_precision='round_trip')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        Xd = torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev)
-        fit = TSNE(perplexity=self.perplexity, max_iter=self.max_iter, init='pca').fit(Xd)
+        if self._left_alone(overwrite, [map_csv, kl_csv] + ([quality_csv] if self.quality_k else [])):
+            return self._table_on_disk()
+        fit = TSNE(perplexity=self.perplexity, max_iter=self.max_iter, init='pca').fit(device_latents(train_data))
         logger.info('t-SNE with perplexity: {}, n_iter: {}, kl: {:.6f}'.format(self.perplexity, fit.n_iter_, fit.kl_divergence_))
         pd.DataFrame({'x': fit.embedding_[:, 0], 'y': fit.embedding_[:, 1]}).to_csv(map_csv, index=False, float_format='%.17g')
         df = pd.DataFrame(fit.kl_history_, columns=['iteration', 'kl'])
@@ -1062,30 +946,28 @@ class Tsne(object):
         return df
 
 
-class Lof(object):
+class Lof(_Branch):
     """--outlier lof: the local outlier factor of the training latents at every k of ``ks`` from one neighbour join (``lof.LofSweep``).  Writes
     plot/lof.csv (per k ``lof_k<k>`` = -negative_outlier_factor_ as %.17g and ``outlier_k<k>`` = 0 / 1, then ``lof_max``; one row per training encounter in
     the cohort's row order) and plot/lof_summary.csv (k, offset, n_outliers, max_lof) and returns the latter table.  Existing files are left alone unless
     ``overwrite`` is set; the table on disk is returned then.  ``fit_`` keeps the ``LofSweep`` of the last run that computed one."""
     FILES = ('lof.csv', 'lof_summary.csv')
+    TABLE = 1
 
     def __init__(self, out_path, ks=(20,), contamination='auto'):
         self.ks = sorted(set(int(k) for k in ks))
         self.contamination = contamination
-        self.out_path = osp.join(out_path, 'plot')
-        os.makedirs(self.out_path, exist_ok=True)
+        self._open(out_path)
         self.fit_ = None
 
     def train(self, train_data, valid_data, **kwargs):
         from .lof import LofSweep          # (here, not at module scope: a run without --outlier loads nothing of it)
         overwrite = kwargs.get('overwrite', False)
         self.fit_ = None
-        lof_csv, summary_csv = (osp.join(self.out_path, name) for name in self.FILES)
-        if osp.exists(lof_csv) and osp.exists(summary_csv) and not overwrite:
-            logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(lof_csv))
-            return pd.read_csv(summary_csv, float_precision='round_trip')
-        dev = torch.device('cuda', torch.cuda.current_device())
-        fit = LofSweep(torch.as_tensor(train_data['hidden'], dtype=torch.float32, device=dev), self.ks, contamination=self.contamination)
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        lof_csv, summary_csv = self._paths()
+        fit = LofSweep(device_latents(train_data), self.ks, contamination=self.contamination)
         columns = {}
         for t, k in enumerate(self.ks):
             columns['lof_k{}'.format(k)] = -fit.nof[:, t]
@@ -1102,40 +984,39 @@ class Lof(object):
         return df
 
 
-class Consensus(object):
+class Consensus(_Branch):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
     labels of either cohort to ``raw_path``/<cohort>_consensus.csv (columns k2..k<k_max>), the file p4's consensus branch reads.  A cohort whose files exist
     is left alone unless ``overwrite`` is set.  Returns the area table (read back from disk when it was left alone); ``fits_`` keeps the fits of this run."""
 
+    FILES = ('consensus_cdf.csv', 'consensus_area.csv')          # (beside them: one raw label file per cohort, under ``raw_path``)
+    TABLE = 1
+
     def __init__(self, k_max, out_path, raw_path, reps=100, p_item=0.8, n_init=1, seed=0):
         self.ks = list(range(2, k_max + 1))
         self.reps, self.p_item, self.n_init, self.seed = reps, p_item, n_init, seed
-        self.out_path = osp.join(out_path, 'plot')
+        self._open(out_path)
         self.raw_path = raw_path
-        os.makedirs(self.out_path, exist_ok=True)
         os.makedirs(self.raw_path, exist_ok=True)
         self.fits_ = {}
 
-    def _fit(self, cohort, feat):
+    def _fit(self, cohort, data):
         logger.info('Consensus clustering of the {} cohort: K = {}..{}, {} resamples'.format(cohort, self.ks[0], self.ks[-1], self.reps))
-        dev = torch.device('cuda', torch.cuda.current_device())
         cc = ConsensusKMeans(self.ks, reps=self.reps, p_item=self.p_item, n_init=self.n_init, seed=self.seed)
-        cc.fit(torch.as_tensor(feat, dtype=torch.float32, device=dev))
+        cc.fit(device_latents(data))
         self.fits_[cohort] = cc
         return cc
 
     def train(self, train_data, valid_data, **kwargs):
         overwrite = kwargs.get('overwrite', False)
         self.fits_ = {}
-        cdf_csv, area_csv = osp.join(self.out_path, 'consensus_cdf.csv'), osp.join(self.out_path, 'consensus_area.csv')
+        cdf_csv, area_csv = self._paths()
         for cohort, data in (('training', train_data), ('validation', valid_data)):
             raw_csv = osp.join(self.raw_path, '{}_consensus.csv'.format(cohort))
-            wanted = [raw_csv] + ([cdf_csv, area_csv] if cohort == 'training' else [])
-            if all(osp.exists(f) for f in wanted) and not overwrite:
-                logger.info('Not saved for {}! Because files existed and not allowed for overwrite.'.format(raw_csv))
+            if self._left_alone(overwrite, [raw_csv] + ([cdf_csv, area_csv] if cohort == 'training' else []), raw_csv):          # (per cohort)
                 continue
-            cc = self._fit(cohort, data['hidden'])
+            cc = self._fit(cohort, data)
             pd.DataFrame({'k{}'.format(k): cc.labels_[k] for k in self.ks}).to_csv(raw_csv, index=False)
             if cohort == 'training':
                 grid = np.arange(BINS + 1) / BINS
@@ -1145,7 +1026,33 @@ class Consensus(object):
                 for k in self.ks:
                     logger.info('k: {}, area: {:.5f}, delta_area: {:.5f}'.format(k, cc.area_[k], cc.delta_area_[k]))
             logger.info('Saved for {}!.'.format(raw_csv))
-        return pd.read_csv(area_csv, float_precision='round_trip')          # (%.17g: exact)
+        return self._table_on_disk()          # (%.17g: exact)
+
+
+def _snn_branch(a, d, out, tr, va):
+    k = a.snn_k if a.snn_k is not None else d + 1
+    return Snn(k, a.snn_eps or snn_default_eps(k), a.snn_min_samples if a.snn_min_samples is not None else k // 4, out).train(tr, va)
+
+
+# --cluster_method -> build the branch object from the arguments, feat_dim and the output directory and run it on the training and the validation cohort
+# (the class names are looked up when a branch runs).  A method of METHODS without an entry ('dl') raises in select_opt_k.
+BRANCHES = {
+    'kmeans': lambda a, d, out, tr, va: KM(a.k_max, out, a.internal_metrics, a.n_init, a.gap_b, a.metric_sample).train(tr, va, a.select_opt_k),
+    'dbscan': lambda a, d, out, tr, va: Dbscan(eps_range=np.arange(.5, 5.1, .5), min_samples=d + 1, out_path=out).train(tr, va, a.select_eps),
+    'optics': lambda a, d, out, tr, va: Optics(min_samples=d + 1, cluster_method='xi', out_path=out).train(tr, va),
+    'consensus': lambda a, d, out, tr, va: Consensus(a.k_max, out, osp.join(osp.dirname(out), 'raw_consensus_result'), reps=a.consensus_reps,
+                                                     p_item=a.consensus_p_item).train(tr, va),
+    'hdbscan': lambda a, d, out, tr, va: Hdbscan(min_samples=d + 1, min_cluster_sizes=a.hdbscan_min_cluster_size or [d + 1], out_path=out).train(tr, va),
+    'ward': lambda a, d, out, tr, va: Ward(a.k_max, out, a.internal_metrics, a.metric_sample).train(tr, va),
+    'gmm': lambda a, d, out, tr, va: Gmm(a.k_max, out, a.internal_metrics, a.n_init, a.gmm_covariance_type, a.metric_sample).train(tr, va),
+    'snn': _snn_branch,
+    'spectral': lambda a, d, out, tr, va: Spectral(a.k_max, out, a.internal_metrics, a.spectral_k, a.spectral_assign, a.metric_sample).train(tr, va),
+    'meanshift': lambda a, d, out, tr, va: Meanshift(out, a.internal_metrics, a.meanshift_quantile, a.meanshift_bandwidth, a.meanshift_bin_seeding,
+                                                     bool(a.meanshift_cluster_all), a.metric_sample).train(tr, va),
+    'kmedoids': lambda a, d, out, tr, va: Kmedoids(a.k_max, out, a.internal_metrics, a.metric_sample).train(tr, va),
+    'densitypeaks': lambda a, d, out, tr, va: Densitypeaks(a.dp_k if a.dp_k is not None else a.k_max, out, a.internal_metrics, a.dp_density, a.dp_percent,
+                                                           a.dp_dc, bool(a.dp_halo), a.metric_sample).train(tr, va),
+}
 
 
 class Cluster(object):
@@ -1174,75 +1081,12 @@ class Cluster(object):
                 Tsne(self.out_path, self.args.tsne_perplexity, self.args.tsne_max_iter, getattr(self.args, 'embed_quality_k', None)).train(self.train_data, self.valid_data)
             if getattr(self.args, 'outlier', None) == 'lof' and dist.rank() == 0:          # (an args object from before the flag: no scores)
                 Lof(self.out_path, self.args.outlier_k, self.args.outlier_contamination).train(self.train_data, self.valid_data)
-            if self.args.cluster_method == 'dbscan':
-                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
-                    eps_range = np.arange(.5, 5.1, .5)
-                    db = Dbscan(eps_range=eps_range, min_samples=self.feat_dim + 1, out_path=self.out_path)
-                    results[metric] = db.train(self.train_data, self.valid_data, self.args.select_eps)
-                continue
-            if self.args.cluster_method == 'optics':
-                if dist.rank() == 0:            # one fit, on rank 0; the other ranks wait at main's barrier
-                    op = Optics(min_samples=self.feat_dim + 1, cluster_method='xi', out_path=self.out_path)
-                    results[metric] = op.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'consensus':
-                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
-                    co = Consensus(self.args.k_max, self.out_path, osp.join(self.exp_path, 'out_feat', 'raw_consensus_result'),
-                                   reps=self.args.consensus_reps, p_item=self.args.consensus_p_item)
-                    results[metric] = co.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'hdbscan':
-                if dist.rank() == 0:            # one tree, on rank 0; the other ranks wait at main's barrier
-                    sizes = self.args.hdbscan_min_cluster_size or [self.feat_dim + 1]
-                    hd = Hdbscan(min_samples=self.feat_dim + 1, min_cluster_sizes=sizes, out_path=self.out_path)
-                    results[metric] = hd.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'ward':
-                if dist.rank() == 0:            # one tree, on rank 0; the other ranks wait at main's barrier
-                    wd = Ward(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.metric_sample)
-                    results[metric] = wd.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'gmm':
-                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
-                    gm = Gmm(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gmm_covariance_type,
-                             self.args.metric_sample)
-                    results[metric] = gm.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'snn':
-                if dist.rank() == 0:            # one graph, on rank 0; the other ranks wait at main's barrier
-                    k = self.args.snn_k if self.args.snn_k is not None else self.feat_dim + 1
-                    eps_values = self.args.snn_eps or snn_default_eps(k)
-                    sn = Snn(k, eps_values, self.args.snn_min_samples if self.args.snn_min_samples is not None else k // 4, self.out_path)
-                    results[metric] = sn.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'spectral':
-                if dist.rank() == 0:            # one decomposition, on rank 0; the other ranks wait at main's barrier
-                    sp = Spectral(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.spectral_k, self.args.spectral_assign,
-                                  self.args.metric_sample)
-                    results[metric] = sp.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'meanshift':
-                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
-                    ms = Meanshift(self.out_path, self.args.internal_metrics, self.args.meanshift_quantile, self.args.meanshift_bandwidth,
-                                   self.args.meanshift_bin_seeding, bool(self.args.meanshift_cluster_all), self.args.metric_sample)
-                    results[metric] = ms.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'kmedoids':
-                if dist.rank() == 0:            # one sweep, on rank 0; the other ranks wait at main's barrier
-                    kd = Kmedoids(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.metric_sample)
-                    results[metric] = kd.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method == 'densitypeaks':
-                if dist.rank() == 0:            # one computation, on rank 0; the other ranks wait at main's barrier
-                    dp = Densitypeaks(self.args.dp_k if self.args.dp_k is not None else self.args.k_max, self.out_path, self.args.internal_metrics,
-                                      self.args.dp_density, self.args.dp_percent, self.args.dp_dc, bool(self.args.dp_halo), self.args.metric_sample)
-                    results[metric] = dp.train(self.train_data, self.valid_data)
-                continue
-            if self.args.cluster_method != 'kmeans':
-                raise NotImplementedError("only --cluster_method kmeans, dbscan, optics, consensus, hdbscan, ward, gmm, snn, spectral, meanshift, kmedoids and densitypeaks are on the accelerated path")
-            km = KM(self.args.k_max, self.out_path, self.args.internal_metrics, self.args.n_init, self.args.gap_b,
-                    self.args.metric_sample)
-            results[metric] = km.train(self.train_data, self.valid_data, self.args.select_opt_k)
+            run = BRANCHES.get(self.args.cluster_method)
+            if run is None:
+                raise NotImplementedError('only --cluster_method {} are on the accelerated path'.format(spell(m for m in METHODS if m in BRANCHES)))
+            # kmeans deals its (K, reference set) problems over the ranks; every other branch is one run, on rank 0: the other ranks wait at main's barrier
+            if self.args.cluster_method == 'kmeans' or dist.rank() == 0:
+                results[metric] = run(self.args, self.feat_dim, self.out_path, self.train_data, self.valid_data)
         return results
 
 

@@ -57,14 +57,13 @@ the positive factor, about 1 inside a neighbourhood -- and ``outlier`` (N, nk) b
 'auto', the default, is a factor of 1.5; a float in (0, 0.5] is that share of the training cohort).  Without --outlier nothing changes.
 """
 import argparse
-import copy
 import os
 import os.path as osp
 
 import numpy as np
 import pandas as pd
 
-from . import cluster_stats
+from ._cluster_cli import METHODS, contamination_arg, noise_summary, spell
 from .dbscan import DBSCAN
 from .density_peaks import DensityPeaks
 from .gmm import GaussianMixture
@@ -84,14 +83,9 @@ from .ward import Ward
 np.random.seed(123)        # p4_clustering_final.py:24
 
 
-def contamination_arg(text):
-    """--outlier_contamination: 'auto' or a float (lof.py refuses one outside (0, 0.5])."""
-    return text if text == 'auto' else float(text)
-
-
 def get_arguments(argv=None):
     p = argparse.ArgumentParser()
-    p.add_argument('--cluster_method', default='kmeans', choices=['kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids', 'densitypeaks'])
+    p.add_argument('--cluster_method', default='kmeans', choices=METHODS)
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical', 'full', 'tied'],
                    help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py')
@@ -203,21 +197,52 @@ class Cluster(object):
         label, vote = knn_transfer_labels(train_ref[0], np.asarray(train_ref[1]).astype(np.int64), feat, k)
         return label.astype(np.asarray(train_ref[1]).dtype), vote
 
-    def _density_branch(self, cohorts, overwrite, name, title, fit):
-        """The dbscan, hdbscan and snn branches: ``fit(feat) -> (raw labels, core points or None)`` per cohort, training clusters re-numbered by sbp,
-        validation / test clusters mapped onto the nearest training centre -- or, with --transfer knn, only the training cohort fitted and the others voted
-        (``_knn_labels``).  ``name``: the file name with the cohort left open; ``title``: the method's name in the log."""
-        train_feat_centers = None
-        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
-        train_ref = None
+    @property
+    def knn(self):
+        """--transfer knn (an args object from before the flag: the default, centre)."""
+        return getattr(self.args, 'transfer', 'centre') == 'knn'
+
+    def _reorder(self, model, raw_label):
+        """Re-numbers the clusters of a model of the training cohort by sbp: ``generate_align_map`` of its 0-based training labels, then the model's
+        slots permuted with the map -- by ``model.reorder``, or for KMeans and Ward, which have none, by permuting ``cluster_centers_`` in place -- so
+        that ``predict`` answers in the new ids.  Returns the aligned training labels."""
+        align_map, aligned, _ = self.generate_align_map(raw_label, self.train_data['ob'], self.train_data['padding_mask'])
+        order = np.empty(len(align_map), dtype=np.int64)
+        for old, new in align_map.items():
+            order[new] = old
+        if hasattr(model, 'reorder'):
+            model.reorder(order)
+        else:
+            model.cluster_centers_[:] = model.cluster_centers_[order]
+        return aligned
+
+    def _write_cohorts(self, cohorts, overwrite, name, fill):
+        """Writes ``name.format(cohort)`` for every cohort that has no such file yet (or all, with ``overwrite``): ``fill(cohort, data)`` puts
+        ``cluster_id`` and any extras into the cohort's dict, which is saved without ``ob`` and ``padding_mask``.  A ``fill`` that returns False has
+        nothing to write for its cohort."""
         for cohort, data in cohorts:
             f = osp.join(self.out_path, name.format(cohort))
             if osp.exists(f) and not overwrite:
                 logger.info('Not Save for {}.'.format(f))
                 continue
+            if fill(cohort, data) is False:
+                continue
+            del data['ob'], data['padding_mask']
+            np.save(f, data)
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+
+    def _density_branch(self, cohorts, overwrite, name, title, fit):
+        """The dbscan, hdbscan, snn and spectral branches: ``fit(feat) -> (raw labels, core points or None)`` per cohort, training clusters re-numbered by
+        sbp, validation / test clusters mapped onto the nearest training centre -- or, with --transfer knn, only the training cohort fitted and the others
+        voted (``_knn_labels``).  ``name``: the file name with the cohort left open, without '_knn' and '.npy'; ``title``: the method's name in the log."""
+        name += ('_knn' if self.knn else '') + '.npy'
+        train_feat_centers = train_ref = None
+
+        def fill(cohort, data):
+            nonlocal train_feat_centers, train_ref
             feat = data['hidden']
             n_core = None
-            if knn and cohort != 'training':
+            if self.knn and cohort != 'training':
                 aligned_label, data['cluster_vote'] = self._knn_labels(osp.join(self.out_path, name.format('training')), train_ref, feat)
             else:
                 logger.info('NEW {} model for {}'.format(title, cohort))
@@ -226,45 +251,46 @@ class Cluster(object):
                     _, aligned_label, train_feat_centers = self.generate_align_map(raw_label, data['ob'], data['padding_mask'], feat)
                 else:
                     aligned_label = self.align_labels_with_center(feat, raw_label, train_feat_centers)
-                if knn:
+                if self.knn:
                     train_ref = (feat, aligned_label)
                     data['cluster_vote'] = np.ones(len(aligned_label), dtype=np.float32)
             data['cluster_id'] = aligned_label
-            del data['ob'], data['padding_mask']
-            if n_core is not None:
-                logger.info('core_sample: {}'.format(n_core))
-            n_clusters_ = len(set(aligned_label)) - (1 if -1 in aligned_label else 0)
-            n_noise_ = int(np.sum(aligned_label == -1))
-            keep = aligned_label != -1
-            logger.info('Estimated number of clusters: %d' % n_clusters_)
-            logger.info('Estimated number of noise points: %d' % n_noise_)
-            if n_clusters_ == 0:
-                continue                      # (upstream writes nothing for this cohort either)
-            elif n_clusters_ == 1:
-                logger.info('Skip the Silhouette Coefficient calculation.')
-            else:
-                logger.info('Orginal Sample: {} Silhouette Coefficient: {:.5f}'.format(len(aligned_label), cluster_stats.silhouette_score(feat, aligned_label)))
-                logger.info('Denoise sample: {}, Denoise Silhouette Coefficient: {:.5f}'.format(
-                    int(keep.sum()), cluster_stats.silhouette_score(feat[keep], aligned_label[keep])))
-            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+            return noise_summary(feat, aligned_label, n_core)[0] > 0          # (no cluster: upstream writes nothing for this cohort either)
+        self._write_cohorts(cohorts, overwrite, name, fill)
+
+    def _kmeans(self, cohorts, overwrite):
+        k = self.args.num_clusters
+        logger.info('==> Generate the k-means results with opt-k: {}'.format(k))
+        model = KMeans(n_clusters=k, init='k-means++', n_init=20).fit(self.train_data['hidden'])
+        self._reorder(model, model.predict(self.train_data['hidden']))
+        self._write_cohorts(cohorts, overwrite, '{{}}_{}.npy'.format(k), lambda cohort, data: data.update(cluster_id=model.predict(data['hidden'])))
+
+    def _dl(self, cohorts, overwrite):
+        for cohort, data in cohorts:          # (not _write_cohorts: the file name comes from the cohort's own soft assignment)
+            prob = data['cluster_label'] if self.args.dl_cluster_label_type == 'label' else data['cluster_pred']
+            data['cluster_id'] = np.argmax(prob, 1)
+            del data['cluster_pred'], data['cluster_label']
+            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, prob.shape[1]))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
             np.save(f, data)
+            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
 
     def _dbscan(self, cohorts, overwrite):
         opt_eps = self.args.opt_eps
         logger.info('==> Generate the DBSCAN results with opt-eps: {}'.format(opt_eps))
-        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
 
         def fit(feat):
             db = DBSCAN(opt_eps, feat.shape[-1]).fit(feat)
             return db.labels_, len(db.core_sample_indices_)
-        self._density_branch(cohorts, overwrite, '{{}}_eps-{}{}.npy'.format(opt_eps, '_knn' if knn else ''), 'DBSCAN', fit)
+        self._density_branch(cohorts, overwrite, '{{}}_eps-{}'.format(opt_eps), 'DBSCAN', fit)
 
     def _hdbscan(self, cohorts, overwrite):
         min_samples = self.feat_dim + 1
         mcs = self.args.hdbscan_min_cluster_size if self.args.hdbscan_min_cluster_size is not None else self.feat_dim + 1
         logger.info('==> Generate the HDBSCAN results with min_cluster_size: {}, min_samples: {}'.format(mcs, min_samples))
-        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
-        self._density_branch(cohorts, overwrite, '{{}}_mcs-{}{}.npy'.format(mcs, '_knn' if knn else ''), 'HDBSCAN',
+        self._density_branch(cohorts, overwrite, '{{}}_mcs-{}'.format(mcs), 'HDBSCAN',
                              lambda feat: (HDBSCAN(min_cluster_size=mcs, min_samples=min_samples).fit(feat).labels_, None))
 
     def _snn(self, cohorts, overwrite):
@@ -273,19 +299,17 @@ class Cluster(object):
         eps = self.args.snn_eps if self.args.snn_eps is not None else int(round(k * 0.5))
         ms = self.args.snn_min_samples if self.args.snn_min_samples is not None else k // 4
         logger.info('==> Generate the SNN results with k: {}, eps: {}, min_samples: {}'.format(k, eps, ms))
-        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
 
         def fit(feat):
             sn = SNN(k, eps, ms).fit(feat)
             return sn.labels_, len(sn.core_sample_indices_)
-        self._density_branch(cohorts, overwrite, '{{}}_snn-k{}-eps{}-ms{}{}.npy'.format(k, eps, ms, '_knn' if knn else ''), 'SNN', fit)
+        self._density_branch(cohorts, overwrite, '{{}}_snn-k{}-eps{}-ms{}'.format(k, eps, ms), 'SNN', fit)
 
     def _spectral(self, cohorts, overwrite):
         """The dbscan branch with a spectral partition into --num_clusters groups in place of the density clusters (no noise label, no core points)."""
         K, k, assign = self.args.num_clusters, self.args.spectral_k, self.args.spectral_assign
         logger.info('==> Generate the spectral clustering results with opt-k: {}, neighbours: {}, assign_labels: {}'.format(K, k, assign))
-        knn = getattr(self.args, 'transfer', 'centre') == 'knn'
-        self._density_branch(cohorts, overwrite, '{{}}_spectral-k{}-K{}{}.npy'.format(k, K, '_knn' if knn else ''), 'spectral clustering',
+        self._density_branch(cohorts, overwrite, '{{}}_spectral-k{}-K{}'.format(k, K), 'spectral clustering',
                              lambda feat: (SpectralClustering(K, n_neighbors=k, assign_labels=assign).fit(feat).labels_, None))
 
     def _ward(self, cohorts, overwrite):
@@ -296,20 +320,9 @@ class Cluster(object):
         k = self.args.num_clusters
         logger.info('==> Generate the Ward results with opt-k: {}'.format(k))
         model = Ward(n_clusters=k).fit(self.train_data['hidden'])
-        raw = np.array(model.labels_)
-        align_map, aligned, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
-        independent = copy.deepcopy(model.cluster_centers_)
-        for old, new in align_map.items():
-            model.cluster_centers_[new] = independent[old]
-        for cohort, data in cohorts:
-            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, k))
-            if osp.exists(f) and not overwrite:
-                logger.info('Not Save for {}.'.format(f))
-                continue
-            data['cluster_id'] = aligned if cohort == 'training' else model.predict(data['hidden'])
-            del data['ob'], data['padding_mask']
-            np.save(f, data)
-            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+        aligned = self._reorder(model, np.array(model.labels_))
+        self._write_cohorts(cohorts, overwrite, '{{}}_{}.npy'.format(k),
+                            lambda cohort, data: data.update(cluster_id=aligned if cohort == 'training' else model.predict(data['hidden'])))
 
     def _gmm(self, cohorts, overwrite):
         """The kmeans branch with a Gaussian mixture in place of the centres: fitted on the training cohort, generate_align_map orders the components by sbp
@@ -324,21 +337,9 @@ class Cluster(object):
         if len(set(raw)) != k:
             raise ValueError('the Gaussian mixture left {} of its {} components without a training encounter: choose a smaller --num_clusters'.format(
                 k - len(set(raw)), k))
-        align_map, _, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
-        order = np.empty(k, dtype=np.int64)
-        for old, new in align_map.items():
-            order[new] = old
-        model.reorder(order)
-        for cohort, data in cohorts:
-            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, k))
-            if osp.exists(f) and not overwrite:
-                logger.info('Not Save for {}.'.format(f))
-                continue
-            data['cluster_id'] = model.predict(data['hidden'])
-            data['cluster_prob'] = model.predict_proba(data['hidden']).astype(np.float32)
-            del data['ob'], data['padding_mask']
-            np.save(f, data)
-            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+        self._reorder(model, raw)
+        self._write_cohorts(cohorts, overwrite, '{{}}_{}.npy'.format(k), lambda cohort, data: data.update(
+            cluster_id=model.predict(data['hidden']), cluster_prob=model.predict_proba(data['hidden']).astype(np.float32)))
 
     def _meanshift(self, cohorts, overwrite):
         """The kmeans branch with mean shift in place of k-means: one fit of the training cohort at the given or the estimated bandwidth finds the centres and
@@ -357,20 +358,9 @@ class Cluster(object):
             raise ValueError('mean shift left {} of its {} centres without a training encounter: choose another bandwidth'.format(
                 k - len(set(raw.tolist()) - {-1}), k))
         logger.info('Estimated number of clusters: {}, orphans: {}'.format(k, int(np.sum(raw == -1))))
-        align_map, _, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
-        order = np.empty(k, dtype=np.int64)
-        for old, new in align_map.items():
-            order[new] = old
-        model.reorder(order)
-        for cohort, data in cohorts:
-            f = osp.join(self.out_path, '{}_meanshift-bw{:.6g}.npy'.format(cohort, h))
-            if osp.exists(f) and not overwrite:
-                logger.info('Not Save for {}.'.format(f))
-                continue
-            data['cluster_id'] = model.predict(data['hidden'], orphans=not cluster_all)
-            del data['ob'], data['padding_mask']
-            np.save(f, data)
-            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+        self._reorder(model, raw)
+        self._write_cohorts(cohorts, overwrite, '{{}}_meanshift-bw{:.6g}.npy'.format(h),
+                            lambda cohort, data: data.update(cluster_id=model.predict(data['hidden'], orphans=not cluster_all)))
 
     def _kmedoids(self, cohorts, overwrite):
         """The kmeans branch with k-medoids (PAM) in place of k-means: one fit of the training cohort from BUILD, generate_align_map orders the slots by sbp and
@@ -379,23 +369,13 @@ class Cluster(object):
         k = self.args.num_clusters
         logger.info('==> Generate the k-medoids results with opt-k: {}'.format(k))
         model = KMedoids(n_clusters=k).fit(self.train_data['hidden'])
-        raw = np.array(model.labels_)
-        align_map, _, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
-        order = np.empty(k, dtype=np.int64)
-        for old, new in align_map.items():
-            order[new] = old
-        model.reorder(order)
-        for cohort, data in cohorts:
-            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, k))
-            if osp.exists(f) and not overwrite:
-                logger.info('Not Save for {}.'.format(f))
-                continue
+        self._reorder(model, np.array(model.labels_))
+
+        def fill(cohort, data):
             data['cluster_id'] = model.predict(data['hidden'])
             if cohort == 'training':
                 data['medoid_index'] = model.medoid_indices_.copy()
-            del data['ob'], data['padding_mask']
-            np.save(f, data)
-            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+        self._write_cohorts(cohorts, overwrite, '{{}}_{}.npy'.format(k), fill)
 
     def _densitypeaks(self, cohorts, overwrite):
         """The kmedoids branch with density peaks in place of PAM: one fit of the training cohort, generate_align_map orders the slots by sbp (from the
@@ -404,33 +384,23 @@ class Cluster(object):
         ``center_index``, the rows of the centre encounters in slot order."""
         a = self.args
         k = a.dp_k if getattr(a, 'dp_k', None) is not None else a.num_clusters
-        knn = getattr(a, 'transfer', 'centre') == 'knn'
         logger.info('==> Generate the density-peaks results with k: {}, density: {}'.format(k, a.dp_density))
         model = DensityPeaks(n_clusters=k, density=a.dp_density, dc='auto' if a.dp_dc is None else a.dp_dc, percent=a.dp_percent,
                              halo=bool(a.dp_halo)).fit(self.train_data['hidden'])
-        align_map, _, _ = self.generate_align_map(np.array(model.core_labels_), self.train_data['ob'], self.train_data['padding_mask'])
-        order = np.empty(k, dtype=np.int64)
-        for old, new in align_map.items():
-            order[new] = old
-        model.reorder(order)
+        self._reorder(model, np.array(model.core_labels_))
         train_ref = (np.asarray(self.train_data['hidden']), np.array(model.labels_))
-        for cohort, data in cohorts:
-            f = osp.join(self.out_path, '{}_{}{}.npy'.format(cohort, k, '_knn' if knn else ''))
-            if osp.exists(f) and not overwrite:
-                logger.info('Not Save for {}.'.format(f))
-                continue
+
+        def fill(cohort, data):
             if cohort == 'training':
                 data['cluster_id'] = model.labels_.copy()
                 data['center_index'] = model.center_indices_.copy()
-                if knn:
+                if self.knn:
                     data['cluster_vote'] = np.ones(len(model.labels_), dtype=np.float32)
-            elif knn:
+            elif self.knn:
                 data['cluster_id'], data['cluster_vote'] = self._knn_labels(None, train_ref, data['hidden'])
             else:
                 data['cluster_id'] = model.predict(data['hidden'])
-            del data['ob'], data['padding_mask']
-            np.save(f, data)
-            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+        self._write_cohorts(cohorts, overwrite, '{{}}_{}{}.npy'.format(k, '_knn' if self.knn else ''), fill)
 
     def _embed_tsne(self, cohorts, overwrite):
         """--embed tsne: one exact t-SNE fit of the training cohort (tsne.py: init 'pca', --tsne_perplexity, --tsne_max_iter); the validation and test
@@ -509,20 +479,18 @@ class Cluster(object):
         raw_label[raw_label == tag] = 0
         return abs(raw_label)
 
-    def _consensus(self, overwrite):
+    def _consensus(self, cohorts, overwrite):
         opt_k = self.args.num_clusters
         logger.info('==> Generate the consensus clustering results with opt-k: {}'.format(opt_k))
         train_raw_label = self._raw_consensus('training', self.train_data)
         align_map, _, _ = self.generate_align_map(train_raw_label, self.train_data['ob'], self.train_data['padding_mask'])
-        for cohort, data in zip(COHORTS, [self.train_data, self.valid_data]):
-            f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, opt_k))
-            if osp.exists(f) and not overwrite:
-                logger.info('Not Save for {}.'.format(f))
-                continue
-            data['cluster_id'] = self.renumber_consensus(self._raw_consensus(cohort, data), align_map)
-            del data['ob'], data['padding_mask']
-            logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
-            np.save(f, data)
+        # the training and the validation cohort only: upstream leaves the test cohort out
+        self._write_cohorts(cohorts[:2], overwrite, '{{}}_{}.npy'.format(opt_k),
+                            lambda cohort, data: data.update(cluster_id=self.renumber_consensus(self._raw_consensus(cohort, data), align_map)))
+
+    # --cluster_method -> its branch, called with (cohorts, overwrite).  A method of METHODS without an entry ('optics') raises in pred.
+    BRANCHES = {'kmeans': _kmeans, 'dl': _dl, 'dbscan': _dbscan, 'consensus': _consensus, 'hdbscan': _hdbscan, 'snn': _snn, 'spectral': _spectral,
+                'ward': _ward, 'gmm': _gmm, 'meanshift': _meanshift, 'kmedoids': _kmedoids, 'densitypeaks': _densitypeaks}
 
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)
@@ -540,58 +508,11 @@ class Cluster(object):
                 self._embed_tsne(cohorts, overwrite)
             if getattr(self.args, 'outlier', None) == 'lof':          # (an args object from before the flag: no scores)
                 self._outlier_lof(cohorts, overwrite)
-            if self.args.cluster_method == 'kmeans':
-                k = self.args.num_clusters
-                logger.info('==> Generate the k-means results with opt-k: {}'.format(k))
-                model = KMeans(n_clusters=k, init='k-means++', n_init=20).fit(self.train_data['hidden'])
-                raw = model.predict(self.train_data['hidden'])
-                align_map, _, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
-                independent = copy.deepcopy(model.cluster_centers_)
-                for old, new in align_map.items():
-                    model.cluster_centers_[new] = independent[old]
-                for cohort, data in cohorts:
-                    f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, k))
-                    if osp.exists(f) and not overwrite:
-                        logger.info('Not Save for {}.'.format(f))
-                        continue
-                    data['cluster_id'] = model.predict(data['hidden'])
-                    del data['ob'], data['padding_mask']
-                    np.save(f, data)
-                    logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
-            elif self.args.cluster_method == 'dl':
-                for cohort, data in cohorts:
-                    prob = data['cluster_label'] if self.args.dl_cluster_label_type == 'label' else data['cluster_pred']
-                    data['cluster_id'] = np.argmax(prob, 1)
-                    del data['cluster_pred'], data['cluster_label']
-                    f = osp.join(self.out_path, '{}_{}.npy'.format(cohort, prob.shape[1]))
-                    if osp.exists(f) and not overwrite:
-                        logger.info('Not Save for {}.'.format(f))
-                        continue
-                    np.save(f, data)
-                    logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
-            elif self.args.cluster_method == 'dbscan':
-                self._dbscan(cohorts, overwrite)
-            elif self.args.cluster_method == 'consensus':
-                self._consensus(overwrite)
-            elif self.args.cluster_method == 'hdbscan':
-                self._hdbscan(cohorts, overwrite)
-            elif self.args.cluster_method == 'snn':
-                self._snn(cohorts, overwrite)
-            elif self.args.cluster_method == 'spectral':
-                self._spectral(cohorts, overwrite)
-            elif self.args.cluster_method == 'ward':
-                self._ward(cohorts, overwrite)
-            elif self.args.cluster_method == 'gmm':
-                self._gmm(cohorts, overwrite)
-            elif self.args.cluster_method == 'meanshift':
-                self._meanshift(cohorts, overwrite)
-            elif self.args.cluster_method == 'kmedoids':
-                self._kmedoids(cohorts, overwrite)
-            elif self.args.cluster_method == 'densitypeaks':
-                self._densitypeaks(cohorts, overwrite)
-            else:
-                raise NotImplementedError("only 'kmeans', 'dl', 'dbscan', 'consensus', 'hdbscan', 'snn', 'spectral', 'ward', 'gmm', 'meanshift', 'kmedoids' and 'densitypeaks' are on the accelerated path: upstream's 'optics' branch of p4 is an "
-                                          "empty `pass` (p2 has the OPTICS fit)")
+            branch = self.BRANCHES.get(self.args.cluster_method)
+            if branch is None:
+                raise NotImplementedError("only {} are on the accelerated path: upstream's 'optics' branch of p4 is an empty `pass` (p2 has the OPTICS fit)".format(
+                    spell(repr(m) for m in self.BRANCHES)))
+            branch(self, cohorts, overwrite)
 
 
 def main(args):
