@@ -57,6 +57,33 @@ def metric_log(names, vals):
     return ' '.join('{}: {:.4f}'.format(n, v) for n, v in zip(names, vals))
 
 
+DBCV_COLUMNS = ['labelling', 'n_clusters', 'n_noise', 'n_singletons', 'dbcv']
+DBCV_CLUSTER_COLUMNS = ['labelling', 'cluster', 'size', 'sparseness', 'separation', 'nearest_cluster', 'validity']
+
+
+def dbcv_summary(points, labellings):
+    """--validity dbcv: the DBCV (dbcv.py) of every entry of ``labellings`` ({name: (N,) int labels, -1 for noise}) on ``points`` (a device tensor or a
+    NumPy array, uploaded once), logged, as two lists of rows: ``DBCV_COLUMNS`` -- one per labelling, NaN where it has fewer than two clusters of two
+    members -- and ``DBCV_CLUSTER_COLUMNS``, one per kept cluster.  The exponent is the column count of ``points``."""
+    from . import dbcv          # (here, not at module scope: a run without --validity loads nothing of it)
+    x, width = dbcv._points(points)
+    rows, cluster_rows = [], []
+    for name, labels in labellings.items():
+        labels = np.asarray(labels).astype(np.int64)
+        try:
+            res = dbcv._score(x, width, labels, None)
+        except ValueError as e:
+            logger.info('DBCV of {}: not defined ({})'.format(name, e))
+            ids, counts = np.unique(labels[labels != -1], return_counts=True)
+            rows.append((name, int((counts >= 2).sum()), int((labels == -1).sum()), int((counts == 1).sum()), float('nan')))
+            continue
+        rows.append((name, len(res.cluster_ids), res.n_noise, res.n_singletons, res.score))
+        cluster_rows += [(name, int(c), int(n), s, p, int(q), v) for c, n, s, p, q, v in
+                         zip(res.cluster_ids, res.sizes, res.sparseness, res.separation, res.nearest_cluster, res.validity)]
+        logger.info('DBCV of {}: {:.6f}, clusters: {}, noise: {}, singletons: {}'.format(name, res.score, len(res.cluster_ids), res.n_noise, res.n_singletons))
+    return rows, cluster_rows
+
+
 def noise_summary(points, labels, n_core=None):
     """Logs what upstream's Dbscan.train logs of one labelling with noise (-1) -- the core count where one is given, the clusters, the noise points, then
     either that the silhouette is skipped (one cluster) or the silhouette of all points and of the points without noise -- and returns ``(n_clusters,

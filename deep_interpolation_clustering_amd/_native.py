@@ -172,6 +172,9 @@ SIGNATURES = {
     'dic_tsne_step': (_i, [_p, _p, _p, C.c_int64, C.c_int64, _p, _p, _sz, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p]),
     'dic_lof_lrd': (_i, [_p, _p, C.c_int64, _i, _p, C.c_int64, _p, _i, _p, _p]),
     'dic_lof_scores': (_i, [_p, C.c_int64, _i, _p, C.c_int64, _p, _p, _i, _p, _p]),
+    'dic_dbcv_workspace': (_sz, [C.c_int64, C.c_int64]),
+    'dic_dbcv_core': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, C.c_double, _p, _p, _sz, _p]),
+    'dic_dbcv_separation': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, _p, _p, _p, _p, _p, _sz, _p]),
     'dic_optics_workspace': (_sz, [C.c_int64, _i]),
     'dic_optics_order': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_double, _p, _p, _p, _p, _sz, _p]),
     'dic_hdbscan_workspace': (_sz, [C.c_int64, _i]),

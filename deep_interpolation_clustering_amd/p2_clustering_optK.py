@@ -93,6 +93,13 @@ the more isolated) and ``outlier_k<k>`` (1 where the factor lies beyond the offs
 (0, 0.5] is that share of the cohort), and ``lof_max``, the largest factor over the given k (Breunig's range heuristic).  plot/lof_summary.csv has one
 row per k: k, offset, n_outliers, max_lof.  Nothing is removed from any clustering branch: that stays a join on lof.csv.  Without --outlier nothing changes.
 
+``--validity dbcv`` (no upstream counterpart; beside any --cluster_method): after the branch has run, every column of its plot/<method>_labels.csv is
+scored against the training latents by DBCV (dbcv.py: Density-Based Clustering Validation, one number in [-1, 1] that has a place for noise and does not
+reward convex blobs -- the figure by which labellings of different eps, min_cluster_size or methods can be compared).  plot/dbcv.csv has one row per
+column: labelling, n_clusters, n_noise, n_singletons, dbcv (NaN below two clusters); plot/dbcv_clusters.csv one row per cluster: labelling, cluster, size,
+sparseness, separation, nearest_cluster, validity; both %.17g.  A method that writes no such label file (kmeans, dbscan, optics, consensus) is logged and
+skipped.  Without --validity nothing changes.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -106,7 +113,7 @@ import pandas as pd
 import torch
 
 from . import cluster_stats, dist
-from ._cluster_cli import METHODS, build_metrics, contamination_arg, device_latents, metric_log, metric_values, noise_summary, spell
+from ._cluster_cli import DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS, METHODS, build_metrics, dbcv_summary, contamination_arg, device_latents, metric_log, metric_values, noise_summary, spell
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
 from .density_peaks import density_peaks_sweep
@@ -179,6 +186,8 @@ def get_arguments(argv=None):
     p.add_argument('--outlier', default=None, choices=['lof'],
                    help='(extra) also write the local outlier factor of every training encounter (plot/lof.csv, plot/lof_summary.csv)')
     p.add_argument('--outlier_k', type=int, nargs='+', default=[20], help="(extra) neighbourhood sizes of --outlier lof, one join for all; default 20, sklearn's")
+    p.add_argument('--validity', default=None, choices=['dbcv'],
+                   help="(extra) also score every column of the method's plot/<method>_labels.csv by DBCV (plot/dbcv.csv, plot/dbcv_clusters.csv)")
     p.add_argument('--outlier_contamination', type=contamination_arg, default='auto',
                    help="(extra) --outlier lof: 'auto' (an encounter is an outlier beyond a factor of 1.5) or the share of outliers, a float in (0, 0.5]")
     return p.parse_args(argv)
@@ -984,6 +993,34 @@ class Lof(_Branch):
         return df
 
 
+class Dbcv(_Branch):
+    """--validity dbcv: the DBCV (dbcv.py) of every column of the method's plot/<method>_labels.csv on the training latents, after the branch has run.
+    Writes plot/dbcv.csv (labelling, n_clusters, n_noise, n_singletons, dbcv: one row per column, NaN below two clusters) and plot/dbcv_clusters.csv
+    (labelling, cluster, size, sparseness, separation, nearest_cluster, validity), %.17g, and returns the former table.  A method that writes no such
+    label file is logged and skipped (None).  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then."""
+    FILES = ('dbcv.csv', 'dbcv_clusters.csv')
+
+    def __init__(self, out_path, method):
+        self.method = method
+        self._open(out_path)
+
+    def train(self, train_data, valid_data, **kwargs):
+        labels_csv = osp.join(self.out_path, '{}_labels.csv'.format(self.method))
+        if not osp.exists(labels_csv):
+            logger.info('No DBCV for --cluster_method {}: it writes no {}.'.format(self.method, labels_csv))
+            return None
+        if self._left_alone(kwargs.get('overwrite', False)):
+            return self._table_on_disk()
+        table_csv, clusters_csv = self._paths()
+        labels = pd.read_csv(labels_csv)
+        rows, cluster_rows = dbcv_summary(device_latents(train_data), {name: labels[name].to_numpy() for name in labels.columns})
+        df = pd.DataFrame(rows, columns=DBCV_COLUMNS)
+        df.to_csv(table_csv, index=False, float_format='%.17g')
+        pd.DataFrame(cluster_rows, columns=DBCV_CLUSTER_COLUMNS).to_csv(clusters_csv, index=False, float_format='%.17g')
+        logger.info('Saved for {}!.'.format(table_csv))
+        return df
+
+
 class Consensus(_Branch):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
@@ -1087,6 +1124,8 @@ class Cluster(object):
             # kmeans deals its (K, reference set) problems over the ranks; every other branch is one run, on rank 0: the other ranks wait at main's barrier
             if self.args.cluster_method == 'kmeans' or dist.rank() == 0:
                 results[metric] = run(self.args, self.feat_dim, self.out_path, self.train_data, self.valid_data)
+            if getattr(self.args, 'validity', None) == 'dbcv' and dist.rank() == 0:          # (an args object from before the flag: no scores)
+                Dbcv(self.out_path, self.args.cluster_method).train(self.train_data, self.valid_data)
         return results
 
 

@@ -55,6 +55,10 @@ encounters' positions -- not embedded again; writes <cohort>_tsne.npy with ``enc
 encounters (sklearn's novelty ``score_samples``), one query join per cohort.  Writes <cohort>_lof.npy with ``encounter_id``, ``ks``, ``lof`` (N, nk) f64 --
 the positive factor, about 1 inside a neighbourhood -- and ``outlier`` (N, nk) bool: beyond the TRAINING fit's offset per k (--outlier_contamination:
 'auto', the default, is a factor of 1.5; a float in (0, 0.5] is that share of the training cohort).  Without --outlier nothing changes.
+``--validity dbcv`` (no upstream counterpart; beside any --cluster_method): the labels written for each cohort are scored against that cohort's own
+latents by DBCV (dbcv.py: Density-Based Clustering Validation, one number in [-1, 1] with a place for noise).  Writes <cohort>_dbcv.csv (labelling -- the
+label file's name --, n_clusters, n_noise, n_singletons, dbcv; NaN below two clusters) and <cohort>_dbcv_clusters.csv (labelling, cluster, size,
+sparseness, separation, nearest_cluster, validity), %.17g, left alone unless overwrite.  Without --validity nothing changes.
 """
 import argparse
 import os
@@ -63,7 +67,7 @@ import os.path as osp
 import numpy as np
 import pandas as pd
 
-from ._cluster_cli import METHODS, contamination_arg, noise_summary, spell
+from ._cluster_cli import DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS, METHODS, contamination_arg, dbcv_summary, noise_summary, spell
 from .dbscan import DBSCAN
 from .density_peaks import DensityPeaks
 from .gmm import GaussianMixture
@@ -128,6 +132,8 @@ def get_arguments(argv=None):
     p.add_argument('--outlier', default=None, choices=['lof'],
                    help='(extra) also write the local outlier factor of every cohort (<cohort>_lof.npy): one fit of the training cohort, the others scored against it')
     p.add_argument('--outlier_k', type=int, nargs='+', default=[20], help="(extra) neighbourhood sizes of --outlier lof, one join for all; default 20, sklearn's")
+    p.add_argument('--validity', default=None, choices=['dbcv'],
+                   help='(extra) also score the labels written for each cohort by DBCV on that cohort\'s latents (<cohort>_dbcv.csv, <cohort>_dbcv_clusters.csv)')
     p.add_argument('--outlier_contamination', type=contamination_arg, default='auto',
                    help="(extra) --outlier lof: 'auto' (an encounter is an outlier beyond a factor of 1.5) or the share of outliers in the training cohort, a "
                         'float in (0, 0.5]')
@@ -230,6 +236,21 @@ class Cluster(object):
             del data['ob'], data['padding_mask']
             np.save(f, data)
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+            self._validity_dbcv(cohort, data, f, overwrite)
+
+    def _validity_dbcv(self, cohort, data, label_file, overwrite):
+        """--validity dbcv: the DBCV of the ``cluster_id`` just written to ``label_file`` on the cohort's own latents.  Writes <cohort>_dbcv.csv and
+        <cohort>_dbcv_clusters.csv (``dbcv_summary``'s two tables, %.17g), left alone where both exist unless ``overwrite``."""
+        if getattr(self.args, 'validity', None) != 'dbcv':          # (an args object from before the flag: no scores)
+            return
+        files = [osp.join(self.out_path, '{}_{}.csv'.format(cohort, name)) for name in ('dbcv', 'dbcv_clusters')]
+        if all(osp.exists(f) for f in files) and not overwrite:
+            logger.info('Not Save for {}.'.format(files[0]))
+            return
+        rows, cluster_rows = dbcv_summary(np.asarray(data['hidden'], dtype=np.float32), {osp.basename(label_file): np.asarray(data['cluster_id'])})
+        pd.DataFrame(rows, columns=DBCV_COLUMNS).to_csv(files[0], index=False, float_format='%.17g')
+        pd.DataFrame(cluster_rows, columns=DBCV_CLUSTER_COLUMNS).to_csv(files[1], index=False, float_format='%.17g')
+        logger.info('Cohort DBCV: {} is done. Save to {}'.format(cohort, files[0]))
 
     def _density_branch(self, cohorts, overwrite, name, title, fit):
         """The dbscan, hdbscan, snn and spectral branches: ``fit(feat) -> (raw labels, core points or None)`` per cohort, training clusters re-numbered by
@@ -276,6 +297,7 @@ class Cluster(object):
                 continue
             np.save(f, data)
             logger.info('Cohort clustering: {} is done. Save to {}'.format(cohort, f))
+            self._validity_dbcv(cohort, data, f, overwrite)
 
     def _dbscan(self, cohorts, overwrite):
         opt_eps = self.args.opt_eps

@@ -1064,6 +1064,36 @@ int dic_lof_lrd(const double* dist, const int32_t* idx, int64_t M, int ld, const
 int dic_lof_scores(const int32_t* idx, int64_t M, int ld, const double* lrd_fit, int64_t n, const double* lrd_rows, const int* ks, int nk, double* nof,
                    dic_stream_t stream);
 
+/* DBCV, Density-Based Clustering Validation (Moulavi, Jaskowiak, Campello, Zimek, Sander, SDM 2014; csrc/dic_dbcv.hip, dbcv.py), stated here once.
+ *   Inputs: points X (N, D <= 256) f32; labels, -1 for noise, any other ids; dpow, the number of features used as the exponent (the caller's column count,
+ *       not the padded D).  d(o, p) is the f64 difference-form distance of the f32 coordinates.  A cluster with one member is treated as noise: it contributes
+ *       0 and counts in N.  Fewer than two remaining clusters: an error of the caller.
+ *   All-points core distance of o in cluster C (n = |C| >= 2), over the other members p of C with d(o, p) > 0 (coincident members are skipped):
+ *       m = the smallest such distance;  S = sum_p (m / d(o, p))^dpow, each term formed as exp(dpow / 2 * log(m^2 / d^2(o, p)));
+ *       a(o) = m (S / (n - 1))^(-1 / dpow);  a(o) = 0 where no member lies at a nonzero distance.
+ *       (The paper's (sum (1 / d)^dpow / (n - 1))^(-1 / dpow) with the largest term factored out: every term lies in (0, 1], nothing leaves f64's range.)
+ *   Within a cluster: mr(o, p) = max(a(o), a(p), d(o, p)).  The spanning tree is the one dic_hdbscan_mst walks over the cluster's members in ascending row
+ *       order from its first member with core = a (ties: the smallest index).  Internal nodes: tree degree >= 2; none: the first member.  Internal edges:
+ *       both ends internal; none: all edges.  DSC(C) = the largest internal edge weight.
+ *   Between clusters: sep(C) = min over internal o in C and internal p of any other (non-noise, non-singleton) cluster of max(a(o), a(p), d(o, p)).
+ *       V(C) = (sep - DSC) / max(sep, DSC), 0 where both are 0.  DBCV = sum_C |C| / N V(C), N counting every row, noise included.
+ * Both entry points take the rows SORTED by (cluster, row), noise and singletons left out by the caller: X (N, D) f32 DEVICE, row stride ldx floats, D % 4 == 0,
+ * ldx % 4 == 0, 16-B aligned (zero columns change nothing), 1 <= N < 2^30; seg_start (K + 1) int32 DEVICE, ascending, seg_start[0] = 0, seg_start[K] = N:
+ * segment s is rows seg_start[s] .. seg_start[s + 1] - 1, 1 <= K <= N.  The CONTENTS of seg_start are not validated (no wild access whatever they are).
+ * workspace: dic_dbcv_workspace(N, K) bytes DEVICE, 16-B aligned, no state between calls.  A pair's d^2 is one f64 fma chain over the coordinates in order
+ * 0 .. D - 1.  No floating-point atomics; two calls give the same bits, whatever the launch geometry.  Nothing synchronises `stream`.
+ *   dic_dbcv_core: a (N) f64 OVERWRITTEN, as defined above; only pairs inside a segment are touched.  1 <= dpow <= 65536.  Terms of S below e^-60 are left
+ *       out (fewer than 2^30 of them against S >= 1: a moves by less than 1e-17 / dpow relatively).
+ *   dic_dbcv_separation: a (N) f64 and internal (N) uint8 (nonzero: the row is an internal node) in; rowsep (N) f64 and rowarg (N) int32 OVERWRITTEN:
+ *       rowsep[o] = min over flagged rows p of OTHER segments of max(a[o], a[p], d(o, p)) and rowarg[o] the p that attains it, the smallest among equals; a
+ *       row with no flagged row in another segment gets +inf and -1.  Every row o gets a value, flagged or not.  The flagged rows are first gathered into
+ *       an ascending list in the workspace and only they are walked as columns: the pass costs N x #flagged pairs. */
+size_t dic_dbcv_workspace(int64_t N, int64_t K);
+int dic_dbcv_core(const float* X, long ldx, int64_t N, int D, const int32_t* seg_start, int64_t K, double dpow, double* a, void* workspace,
+                  size_t workspace_bytes, dic_stream_t stream);
+int dic_dbcv_separation(const float* X, long ldx, int64_t N, int D, const int32_t* seg_start, int64_t K, const double* a, const unsigned char* internal,
+                        double* rowsep, int32_t* rowarg, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
