@@ -84,6 +84,90 @@ def dbcv_summary(points, labellings):
     return rows, cluster_rows
 
 
+AGREEMENT_INDICES = ('ari', 'ami', 'nmi', 'rand', 'fmi', 'vmeasure')
+AGREEMENT_COLUMNS = ['labelling_a', 'labelling_b', 'n', 'clusters_a', 'clusters_b']          # (then the requested indices, in the order asked for)
+
+
+def add_agreement_arguments(p, what):
+    """The three --agreement flags of p2 and p4; ``what``: which labellings the program compares, for the help text."""
+    p.add_argument('--agreement', nargs='+', default=None, choices=list(AGREEMENT_INDICES), metavar='INDEX',
+                   help='(extra) also compare {} with each other by these indices ({})'.format(what, ' '.join(AGREEMENT_INDICES)))
+    p.add_argument('--agreement_scope', default='all', choices=['all', 'method'],
+                   help="(extra) --agreement: the labellings of every method's output directory that exists (all, the default) or of this --cluster_method only")
+    p.add_argument('--agreement_noise', default='class', choices=['class', 'drop'],
+                   help="(extra) --agreement: -1 is a class like any other (class, sklearn's behaviour) or, per pair, rows with -1 in either labelling are left out")
+
+
+def agreement_summary(labellings, indices, noise='class'):
+    """--agreement: every unordered pair of ``labellings`` ({name: (N,) int labels}; uploaded once) compared by ``indices`` (agreement.py), one log line
+    per pair.  Returns the rows of the long table -- ``AGREEMENT_COLUMNS`` then the indices -- and ``{index: (L, L) matrix}``, the diagonal from the same
+    kernels."""
+    from . import agreement          # (here, not at module scope: a run without --agreement loads nothing of it)
+    indices = list(indices)
+    res = agreement.agreement_matrix(labellings, indices=indices, noise=noise)
+    rows = []
+    for p, (i, j) in enumerate(res.pairs):
+        vals = [float(res.values[name][p]) for name in indices]
+        rows.append((res.names[i], res.names[j], int(res.n[p]), int(res.n_clusters[p, 0]), int(res.n_clusters[p, 1])) + tuple(vals))
+        logger.info('agreement of {} and {}: rows: {}, clusters: {} / {}, {}'.format(res.names[i], res.names[j], int(res.n[p]), int(res.n_clusters[p, 0]),
+                                                                                      int(res.n_clusters[p, 1]), metric_log(indices, vals)))
+    return rows, {name: res[name] for name in indices}
+
+
+def _integer_columns(csv, prefix, n_rows, out):
+    """Adds the columns of a label table to ``out`` as ``<prefix>:<column>``; a file of another row count, or a column that holds no integers, is logged
+    and skipped."""
+    import pandas as pd
+    table = pd.read_csv(csv)
+    if len(table) != n_rows:
+        logger.info('No agreement for {}: {} rows against the {} of the training cohort.'.format(csv, len(table), n_rows))
+        return
+    for column in table.columns:
+        values = table[column].to_numpy()
+        if not np.issubdtype(values.dtype, np.integer):
+            logger.info('No agreement for column {} of {}: it holds no integers.'.format(column, csv))
+            continue
+        out['{}:{}'.format(prefix, column)] = values.astype(np.int64)
+
+
+def training_labellings(out_feat, metric, methods, n_rows, consensus=True):
+    """p2 --agreement: ``{'<method>:<column>': labels}`` from every ``<out_feat>/<metric>_<m>_aligned/plot/<m>_labels.csv`` that exists for m in ``methods``,
+    and with ``consensus`` the columns of ``<out_feat>/raw_consensus_result/training_consensus.csv`` as ``consensus:k<K>``."""
+    import os.path as osp
+    out = {}
+    for m in methods:
+        csv = osp.join(out_feat, '{}_{}_aligned'.format(metric, m), 'plot', '{}_labels.csv'.format(m))
+        if osp.exists(csv):
+            _integer_columns(csv, m, n_rows, out)
+    raw = osp.join(out_feat, 'raw_consensus_result', 'training_consensus.csv')
+    if consensus and osp.exists(raw):
+        _integer_columns(raw, 'consensus', n_rows, out)
+    return out
+
+
+def cohort_labellings(out_feat, metric, methods, cohort, encounter_id):
+    """p4 --agreement: ``{'<method>/<file stem>': cluster_id}`` from every ``<out_feat>/<metric>_<m>_aligned/<cohort>_*.npy`` for m in ``methods`` that
+    holds a ``cluster_id`` and the same ``encounter_id`` array as the cohort; any other file is logged and skipped."""
+    import glob
+    import os.path as osp
+    out = {}
+    encounter_id = np.asarray(encounter_id)
+    for m in methods:
+        for f in sorted(glob.glob(osp.join(out_feat, '{}_{}_aligned'.format(metric, m), '{}_*.npy'.format(cohort)))):
+            try:
+                saved = np.load(f, allow_pickle=True).item()
+            except (ValueError, AttributeError):          # (an array, not a dict: a map)
+                saved = None
+            if not isinstance(saved, dict) or 'cluster_id' not in saved or 'encounter_id' not in saved:
+                continue
+            ids = np.asarray(saved['cluster_id'])
+            if not np.array_equal(np.asarray(saved['encounter_id']), encounter_id) or ids.shape != encounter_id.shape or not np.issubdtype(ids.dtype, np.integer):
+                logger.info('No agreement for {}: other encounters than the {} cohort, or no integer labels.'.format(f, cohort))
+                continue
+            out['{}/{}'.format(m, osp.splitext(osp.basename(f))[0])] = ids.astype(np.int64)
+    return out
+
+
 def noise_summary(points, labels, n_core=None):
     """Logs what upstream's Dbscan.train logs of one labelling with noise (-1) -- the core count where one is given, the clusters, the noise points, then
     either that the silhouette is skipped (one cluster) or the silhouette of all points and of the points without noise -- and returns ``(n_clusters,

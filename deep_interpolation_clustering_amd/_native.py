@@ -175,6 +175,11 @@ SIGNATURES = {
     'dic_dbcv_workspace': (_sz, [C.c_int64, C.c_int64]),
     'dic_dbcv_core': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, C.c_double, _p, _p, _sz, _p]),
     'dic_dbcv_separation': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_int64, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_agreement_lds_cells': (_i, []),
+    'dic_agreement_workspace': (_sz, [C.c_int64]),
+    'dic_agreement_tables': (_i, [_p, C.c_int64, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p]),
+    'dic_agreement_sums': (_i, [_p, C.c_int64, _p, C.c_int64, C.c_int64, _p, C.c_int64, _p, _p, _p]),
+    'dic_agreement_emi': (_i, [_p, C.c_int64, _p, C.c_int64, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, _p, _sz, _p]),
     'dic_optics_workspace': (_sz, [C.c_int64, _i]),
     'dic_optics_order': (_i, [_p, C.c_long, C.c_int64, _i, _p, C.c_double, _p, _p, _p, _p, _sz, _p]),
     'dic_hdbscan_workspace': (_sz, [C.c_int64, _i]),

@@ -100,6 +100,15 @@ column: labelling, n_clusters, n_noise, n_singletons, dbcv (NaN below two cluste
 sparseness, separation, nearest_cluster, validity; both %.17g.  A method that writes no such label file (kmeans, dbscan, optics, consensus) is logged and
 skipped.  Without --validity nothing changes.
 
+``--agreement INDEX [INDEX ...]`` (ari ami nmi rand fmi vmeasure; no upstream counterpart; beside any --cluster_method): after the branch and --validity
+have run, the TRAINING labellings are compared with each other, every unordered pair (agreement.py: sklearn.metrics.cluster's indices, all pairs in one
+launch per stage).  --agreement_scope method: the columns of this run's plot/<method>_labels.csv; all (the default): the columns of every
+<metric>_<m>_aligned/plot/<m>_labels.csv that exists, and those of raw_consensus_result/training_consensus.csv as consensus:k<K>.  A labelling is named
+<method>:<column>; a file of another row count than the training cohort is logged and skipped; fewer than two labellings: logged, nothing written.
+--agreement_noise class (the default: -1 is a class, as in sklearn) or drop (per pair, rows with -1 in either labelling are left out).  plot/agreement.csv
+has one row per pair: labelling_a, labelling_b, n, clusters_a, clusters_b, then the indices; plot/agreement_<index>.csv is the square table of one index,
+the names as header and first column; all %.17g.  Without --agreement nothing changes.
+
 The seaborn plots of the upstream script are not provided.
 """
 import argparse
@@ -113,7 +122,7 @@ import pandas as pd
 import torch
 
 from . import cluster_stats, dist
-from ._cluster_cli import DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS, METHODS, build_metrics, dbcv_summary, contamination_arg, device_latents, metric_log, metric_values, noise_summary, spell
+from ._cluster_cli import AGREEMENT_COLUMNS, DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS, METHODS, add_agreement_arguments, agreement_summary, build_metrics, dbcv_summary, contamination_arg, device_latents, metric_log, metric_values, noise_summary, spell, training_labellings
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
 from .density_peaks import density_peaks_sweep
@@ -188,6 +197,7 @@ def get_arguments(argv=None):
     p.add_argument('--outlier_k', type=int, nargs='+', default=[20], help="(extra) neighbourhood sizes of --outlier lof, one join for all; default 20, sklearn's")
     p.add_argument('--validity', default=None, choices=['dbcv'],
                    help="(extra) also score every column of the method's plot/<method>_labels.csv by DBCV (plot/dbcv.csv, plot/dbcv_clusters.csv)")
+    add_agreement_arguments(p, 'the training labellings on disk (plot/agreement.csv, plot/agreement_<index>.csv)')
     p.add_argument('--outlier_contamination', type=contamination_arg, default='auto',
                    help="(extra) --outlier lof: 'auto' (an encounter is an outlier beyond a factor of 1.5) or the share of outliers, a float in (0, 0.5]")
     return p.parse_args(argv)
@@ -1021,6 +1031,38 @@ class Dbcv(_Branch):
         return df
 
 
+class Agreement(_Branch):
+    """--agreement: the training labellings on disk compared with each other (agreement.py), after the branch and --validity have run.  ``scope`` 'method':
+    the columns of this run's plot/<method>_labels.csv; 'all': those of every method's label file under the same out_feat directory and of the training
+    consensus labels (``training_labellings``).  Writes plot/agreement.csv (one row per unordered pair: labelling_a, labelling_b, n, clusters_a, clusters_b,
+    then the indices) and one square plot/agreement_<index>.csv per index (the names as header and first column), %.17g, and returns the former table.
+    Fewer than two labellings: logged, nothing written (None).  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then."""
+
+    def __init__(self, out_path, method, indices, scope='all', noise='class'):
+        self.method, self.indices, self.scope, self.noise = method, list(dict.fromkeys(indices)), scope, noise
+        self.FILES = ('agreement.csv',) + tuple('agreement_{}.csv'.format(name) for name in self.indices)
+        self.metric = osp.basename(out_path)[:-len('_{}_aligned'.format(method))]
+        self.out_feat = osp.dirname(out_path)
+        self._open(out_path)
+
+    def train(self, train_data, valid_data, **kwargs):
+        if self._left_alone(kwargs.get('overwrite', False)):
+            return self._table_on_disk()
+        everything = self.scope == 'all'
+        labellings = training_labellings(self.out_feat, self.metric, METHODS if everything else [self.method], len(train_data['encounter_id']), everything)
+        if len(labellings) < 2:
+            logger.info('No agreement: {} labelling of the training cohort on disk, two are needed.'.format(len(labellings)))
+            return None
+        rows, squares = agreement_summary(labellings, self.indices, self.noise)
+        paths = self._paths()
+        df = pd.DataFrame(rows, columns=AGREEMENT_COLUMNS + self.indices)
+        df.to_csv(paths[0], index=False, float_format='%.17g')
+        for name, f in zip(self.indices, paths[1:]):
+            pd.DataFrame(squares[name], index=list(labellings), columns=list(labellings)).to_csv(f, index_label='labelling', float_format='%.17g')
+        logger.info('Saved for {}!.'.format(paths[0]))
+        return df
+
+
 class Consensus(_Branch):
     """Consensus clustering of the training and of the validation latents for K = 2..k_max, each cohort on its own (``consensus.ConsensusKMeans``).  Writes the
     training cohort's CDFs to plot/consensus_cdf.csv (k, c, cdf) and areas to plot/consensus_area.csv (k, area, delta_area) under ``out_path``, and the 1-based
@@ -1126,6 +1168,9 @@ class Cluster(object):
                 results[metric] = run(self.args, self.feat_dim, self.out_path, self.train_data, self.valid_data)
             if getattr(self.args, 'validity', None) == 'dbcv' and dist.rank() == 0:          # (an args object from before the flag: no scores)
                 Dbcv(self.out_path, self.args.cluster_method).train(self.train_data, self.valid_data)
+            if getattr(self.args, 'agreement', None) and dist.rank() == 0:          # (an args object from before the flag: no tables)
+                Agreement(self.out_path, self.args.cluster_method, self.args.agreement, getattr(self.args, 'agreement_scope', 'all'),
+                          getattr(self.args, 'agreement_noise', 'class')).train(self.train_data, self.valid_data)
         return results
 
 

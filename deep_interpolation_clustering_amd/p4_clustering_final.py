@@ -59,6 +59,11 @@ the positive factor, about 1 inside a neighbourhood -- and ``outlier`` (N, nk) b
 latents by DBCV (dbcv.py: Density-Based Clustering Validation, one number in [-1, 1] with a place for noise).  Writes <cohort>_dbcv.csv (labelling -- the
 label file's name --, n_clusters, n_noise, n_singletons, dbcv; NaN below two clusters) and <cohort>_dbcv_clusters.csv (labelling, cluster, size,
 sparseness, separation, nearest_cluster, validity), %.17g, left alone unless overwrite.  Without --validity nothing changes.
+``--agreement INDEX [INDEX ...]`` (ari ami nmi rand fmi vmeasure; no upstream counterpart; beside any --cluster_method): for each cohort, once its label
+file is written, every <metric>_<m>_aligned/<cohort>_*.npy (--agreement_scope method: this method's directory only) that holds a ``cluster_id`` and the
+cohort's own ``encounter_id`` array is compared with every other (agreement.py), named <method>/<file stem>.  Writes <cohort>_agreement.csv: one row per
+unordered pair -- labelling_a, labelling_b, n, clusters_a, clusters_b, then the indices, %.17g --, left alone unless overwrite.  --agreement_noise class
+(the default: -1 is a class, as in sklearn) or drop.  Labellings of DIFFERENT cohorts are not compared.  Without --agreement nothing changes.
 """
 import argparse
 import os
@@ -67,7 +72,8 @@ import os.path as osp
 import numpy as np
 import pandas as pd
 
-from ._cluster_cli import DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS, METHODS, contamination_arg, dbcv_summary, noise_summary, spell
+from ._cluster_cli import (AGREEMENT_COLUMNS, DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS, METHODS, add_agreement_arguments, agreement_summary, cohort_labellings,
+                           contamination_arg, dbcv_summary, noise_summary, spell)
 from .dbscan import DBSCAN
 from .density_peaks import DensityPeaks
 from .gmm import GaussianMixture
@@ -137,6 +143,7 @@ def get_arguments(argv=None):
     p.add_argument('--outlier_contamination', type=contamination_arg, default='auto',
                    help="(extra) --outlier lof: 'auto' (an encounter is an outlier beyond a factor of 1.5) or the share of outliers in the training cohort, a "
                         'float in (0, 0.5]')
+    add_agreement_arguments(p, "each cohort's label files on disk (<cohort>_agreement.csv)")
     return p.parse_args(argv)
 
 
@@ -251,6 +258,25 @@ class Cluster(object):
         pd.DataFrame(rows, columns=DBCV_COLUMNS).to_csv(files[0], index=False, float_format='%.17g')
         pd.DataFrame(cluster_rows, columns=DBCV_CLUSTER_COLUMNS).to_csv(files[1], index=False, float_format='%.17g')
         logger.info('Cohort DBCV: {} is done. Save to {}'.format(cohort, files[0]))
+
+    def _agreement(self, cohorts, overwrite):
+        """--agreement: per cohort, the label files on disk (``cohort_labellings``) compared with each other.  Writes <cohort>_agreement.csv
+        (``agreement_summary``'s long table, %.17g), left alone where it exists unless ``overwrite``; fewer than two labellings: logged, nothing written."""
+        indices = list(dict.fromkeys(self.args.agreement))
+        methods = METHODS if getattr(self.args, 'agreement_scope', 'all') == 'all' else [self.args.cluster_method]
+        metric = osp.basename(self.feat_path)
+        for cohort, data in cohorts:
+            f = osp.join(self.out_path, '{}_agreement.csv'.format(cohort))
+            if osp.exists(f) and not overwrite:
+                logger.info('Not Save for {}.'.format(f))
+                continue
+            labellings = cohort_labellings(osp.dirname(self.out_path), metric, methods, cohort, data['encounter_id'])
+            if len(labellings) < 2:
+                logger.info('No agreement for the {} cohort: {} labelling on disk, two are needed.'.format(cohort, len(labellings)))
+                continue
+            rows, _ = agreement_summary(labellings, indices, getattr(self.args, 'agreement_noise', 'class'))
+            pd.DataFrame(rows, columns=AGREEMENT_COLUMNS + indices).to_csv(f, index=False, float_format='%.17g')
+            logger.info('Cohort agreement: {} is done. Save to {}'.format(cohort, f))
 
     def _density_branch(self, cohorts, overwrite, name, title, fit):
         """The dbscan, hdbscan, snn and spectral branches: ``fit(feat) -> (raw labels, core points or None)`` per cohort, training clusters re-numbered by
@@ -535,6 +561,8 @@ class Cluster(object):
                 raise NotImplementedError("only {} are on the accelerated path: upstream's 'optics' branch of p4 is an empty `pass` (p2 has the OPTICS fit)".format(
                     spell(repr(m) for m in self.BRANCHES)))
             branch(self, cohorts, overwrite)
+            if getattr(self.args, 'agreement', None):          # (an args object from before the flag: no tables)
+                self._agreement(cohorts, overwrite)
 
 
 def main(args):

@@ -1094,6 +1094,48 @@ int dic_dbcv_core(const float* X, long ldx, int64_t N, int D, const int32_t* seg
 int dic_dbcv_separation(const float* X, long ldx, int64_t N, int D, const int32_t* seg_start, int64_t K, const double* a, const unsigned char* internal,
                         double* rowsep, int32_t* rowarg, void* workspace, size_t workspace_bytes, dic_stream_t stream);
 
+/* Agreement of two labellings a, b of the same N rows (csrc/dic_agreement.hip, agreement.py): sklearn 1.7.2's sklearn.metrics.cluster, stated here once, for
+ * P pairs of the L rows of one code matrix in one launch per stage.
+ *   Inputs: codes (L, N) int32 DEVICE, row stride ld: row l holds the class of every row of the data under labelling l as a code in [0, K_l) (the caller
+ *       encodes; -1 is a class like any other).  drop (L) int32 DEVICE or NULL: a row whose code under EITHER labelling of a pair equals that labelling's
+ *       drop[l] is left out of the pair (-1: nothing to drop).  A code outside [0, K_l) is skipped: no wild access.
+ *   desc (P, 8) int64 DEVICE, one row per pair: {la, lb, Ka, Kb, table_off, marg_off, part_off, 0}: the pair's table n (Ka, Kb) int32 row-major starts at
+ *       tables + table_off, its marginals a (Ka) then b (Kb) int64 at marg + marg_off, its Ka * ceil(Kb / 64) EMI partials at double word part_off of the
+ *       workspace.  A pair whose descriptor points outside a buffer (total_cells, total_marg, the workspace) or has la, lb outside [0, L) is SKIPPED by
+ *       every stage and its outputs are left as they were.  1 <= L, P < 2^24; N < 2^31.
+ *   Per pair: n_ij = #{r : a_r = i, b_r = j};  a_i = sum_j n_ij;  b_j = sum_i n_ij;  N' = sum_ij n_ij (the rows counted: N without drop).
+ *       isums = {sum_ij n_ij^2, sum_i a_i^2, sum_j b_j^2, N'} int64.  (Pair confusion, Rand, ARI and FMI are integer expressions of these: agreement.py.)
+ *       MI = sum over the cells with n_ij > 0 of t_ij, in f64 with sklearn's grouping (cnm = n_ij / N', every log of the integer converted to f64,
+ *           a_i * b_j formed in int64):
+ *               t_ij = cnm * (log(n_ij) - log(N')) + cnm * ((-log(a_i * b_j) + log(N')) + log(N')),  set to 0 where |t_ij| < 2^-52;
+ *           no fused multiply-add.  ORDER: thread t of 256 adds the cells c = t, t + 256, .. of the row-major table in ascending order, starting from 0; the
+ *           256 sums are then added by a binary tree, x[t] += x[t + s] for s = 128, 64, .., 1.
+ *       H(a) = -sum_{a_i > 0} (a_i / N') * (log(a_i) - log(N')), thread t adding i = t, t + 256, .., then the same tree and one negation; H(b) likewise.
+ *       EMI = sum over ALL cells (i, j) with a_i, b_j > 0 and n = max(1, a_i + b_j - N') .. min(a_i, b_j) of
+ *               ((n / N') * (((log(N') + log(n)) - log(a_i)) - log(b_j))) * exp(g),  with lf[m] = ln m! the CALLER's table (lf_len >= N' + 1 doubles) and
+ *               g = ((((((lf[a_i] + lf[b_j]) + lf[N' - a_i]) + lf[N' - b_j]) - (lf[n] + lf[N'])) - lf[a_i - n]) - lf[b_j - n]) - lf[N' - a_i - b_j + n]
+ *           -- sklearn's order of the nine terms.  Terms with g < -746 are left out: exp is exactly 0 there, no bit changes.
+ *           ORDER: a unit u = i * ceil(Kb / 64) + c is row i and the columns j = 64 c .. 64 c + 63 of the table, summed by the 64 lanes of one wave, each
+ *           lane from 0: where a_i <= 32, lane l takes column 64 c + l and adds its n ascending; else the columns are taken in ascending order and within one
+ *           lane l adds n = lo + l, lo + l + 64, ..  The 64 lane sums are added by the butterfly x += x[lane ^ m], m = 32, 16, .., 1, which gives the unit's
+ *           partial.  Thread t of 256 adds the partials u = t, t + 256, .. ascending, then the binary tree above.
+ *   Integer adds commute (integer LDS / global atomics only), no floating-point atomics: two calls give the same bits, and a pair's results do not depend on
+ *   which other pairs share the call.  Nothing synchronises `stream`.
+ *   dic_agreement_lds_cells: the largest table (Ka * Kb cells) that is counted in LDS and flushed once per workgroup; a larger one is counted in global memory.
+ *   dic_agreement_workspace(total_units): bytes DEVICE, 16-B aligned, for the EMI partials of all pairs (total_units = sum over pairs of Ka * ceil(Kb / 64)).
+ *   dic_agreement_tables: tables (total_cells) int32 OVERWRITTEN (zeroed, then counted).
+ *   dic_agreement_sums: marg (total_marg) int64, isums (P, 4) int64 and fsums (P, 3) f64 = {MI, H(a), H(b)} OVERWRITTEN for every pair that is not skipped.
+ *   dic_agreement_emi: marg and isums as dic_agreement_sums left them; max_units the largest Ka * ceil(Kb / 64) of the pairs (< 2^26); emi (P) f64
+ *       OVERWRITTEN.  A pair with N' >= lf_len gets NaN. */
+int dic_agreement_lds_cells(void);
+size_t dic_agreement_workspace(int64_t total_units);
+int dic_agreement_tables(const int32_t* codes, int64_t ld, int64_t L, int64_t N, const int32_t* drop, const int64_t* desc, int64_t P, int32_t* tables,
+                         int64_t total_cells, dic_stream_t stream);
+int dic_agreement_sums(const int32_t* tables, int64_t total_cells, const int64_t* desc, int64_t L, int64_t P, int64_t* marg, int64_t total_marg,
+                       int64_t* isums, double* fsums, dic_stream_t stream);
+int dic_agreement_emi(const int64_t* marg, int64_t total_marg, const int64_t* desc, int64_t L, int64_t P, int64_t max_units, const int64_t* isums,
+                      const double* lf, int64_t lf_len, double* emi, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
