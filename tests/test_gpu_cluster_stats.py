@@ -171,6 +171,34 @@ def test_row_sums_on_the_matrix_cores_match_the_difference_form(cs, n, d, k, spr
         np.testing.assert_allclose(cs.silhouette_score(x, lab, got), cs.silhouette_score(x, lab, want), rtol=1e-5, atol=2e-6 if n >= 8192 else 2e-5)
 
 
+@pytest.fixture(scope='module')
+def rec():
+    """scripts/record_intra_golden.py: the cases' inputs and how an output is reduced to what the fixture holds."""
+    import runpy
+    from types import SimpleNamespace
+    return SimpleNamespace(**runpy.run_path(os.path.join(os.path.dirname(GOLDEN), os.pardir, 'scripts', 'record_intra_golden.py')))
+
+
+INTRA_TOTALS = [(700, 36, 3), (1537, 20, 64), (513, 255, 2), (5900, 8, 1)]
+INTRA_ROWSUMS = [(700, 36, 3), (1537, 20, 64), (4400, 8, 3)]
+
+
+@pytest.mark.parametrize('kind,n,d,k', [('totals',) + c for c in INTRA_TOTALS] + [('rowsums',) + c for c in INTRA_ROWSUMS])
+def test_intra_passes_equal_the_recorded_bits(cs, rec, kind, n, d, k, monkeypatch):
+    """dic_cluster_intra_totals / dic_cluster_pair_rowsums against tests/golden/intra_pairtile_parent.npz, BIT for bit: what the last commit with a tile loop of
+    its own in dic_intra.hip computed on an MI355X (scripts/record_intra_golden.py).  The move onto dic_pairtile.h reorders no floating-point operation.  Totals:
+    a cluster end inside a block, clusters smaller than a block and a singleton, a zero-padded width with a block of one row, 300 tiles on 256 workgroups (the
+    strided assignment wraps).  Row sums (all bytes by SHA-256, and sampled rows): the same small shapes, and more than 256 tiles (contiguous ranges that split a
+    (row block, cluster) run between two workgroups)."""
+    assert (n, d, k) in (rec.TOTALS if kind == 'totals' else rec.ROWSUMS)
+    monkeypatch.setattr(cs, 'ROWSUM_MIN_POINTS', 0)
+    golden = np.load(os.path.join(GOLDEN, 'intra_pairtile_parent.npz'))
+    got = (rec.totals_case if kind == 'totals' else rec.rowsums_case)(cs, n, d, k)
+    assert got
+    for name, value in got.items():
+        assert value.dtype == golden[name].dtype and np.array_equal(value, golden[name]), name
+
+
 def test_gap_table_equals_reference(tmp_path):
     """KM.compute_gap_internal_metric against the table the REFERENCE's own method produced (oracle/make_golden_gap.py; p2:353-410):
     every column at rtol 1e-5 AND the position of NumPy's global stream afterwards -- i.e. the draw order reference set -> that fit's

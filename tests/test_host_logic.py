@@ -275,3 +275,33 @@ def test_distance_pass_tile_lists_cover_every_block_pair_once():
         assert group_start.shape == (n_i * K + 1,) and group_start[0] == 0 and group_start[-1] == n_slots
         for g in range(n_i * K):
             assert sorted(set(slot[group == g])) == list(range(group_start[g], group_start[g + 1]))
+
+
+def test_intra_kernels_scratch_does_not_grow():
+    """A ratchet on the scratch memory of dic_intra.hip (dic_pairtile.h included), compiled with the Makefile's flags: none for any kernel, the two tile kernels
+    included -- what they compiled to with a tile loop of their own (intra_x3_kernel<false> / <true>: 0 and 0 bytes per lane), before they became epilogues of
+    the shared loop."""
+    import re
+    import shutil
+    import subprocess
+
+    import pytest
+    hipcc = shutil.which('hipcc') or '/opt/rocm/bin/hipcc'
+    if not os.path.exists(hipcc):
+        pytest.skip('hipcc not available')
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = os.path.join(root, 'deep_interpolation_clustering_amd', 'csrc')
+    res = subprocess.run([hipcc, '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-I' + os.path.join(root, 'include'), '-c',
+                          os.path.join(src, 'dic_intra.hip'), '-o', os.devnull, '-mllvm', '-disable-lsr', '-Rpass-analysis=kernel-resource-usage'],
+                         capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stderr[-2000:]
+    names = re.findall(r'Function Name: (\S+)', res.stderr)
+    scratch = [int(v) for v in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', res.stderr)]
+    assert len(scratch) == len(names)
+    ceilings = {'intra_totals_kernel': 0, 'intra_rows_kernel': 0}
+    seen = set()
+    for name, got in zip(names, scratch):
+        key = [k for k in ceilings if k in name]
+        seen.update(key)
+        assert got <= (ceilings[key[0]] if key else 0), (name, got)
+    assert seen == set(ceilings), names
