@@ -20,14 +20,13 @@
 //     INVARIANTS:  c_i < k <= c_i + |candidates_i|  (c_i <= #{a <= lo} < k <= #{a <= hi} <= c_i + |candidates_i|), and every pair counted into c_i has exact
 //     d^2 below every candidate that can hold rank k.  Hence V = the (k - c_i)-th smallest exact d^2 among the candidates.  One more counting pass (the two
 //     thresholds wlo, whi) gives c_i and |candidates_i| exactly.
-// (3) GATHER + EXACT, over groups of rows sized by the candidate budget: a gather pass walks the tiles of the group's row blocks and appends every candidate
-//     j to row i's list (list offsets = the prefix sum of the counts of (2), taken on the device; the slot inside a list comes from an integer atomic
-//     cursor -- the order of a list cannot matter, the value at a rank does not depend on it).  The exact kernel computes the f64 difference-form d^2 of every list entry (each term exact,
-//     summed in a fixed order) and selects rank k - c_i by a radix select over the bit patterns of the (non-negative) doubles: the value AT the rank, ties or
-//     not.  The approximate products never decide the rank and never supply the value.
+// (3) GATHER + EXACT, over groups of rows sized by the candidate budget (dic_candlist.h has the protocol, what the budget can change and the guards): the
+//     list lengths are the counts of (2); the gather pass appends every candidate j to row i's list; the exact kernel computes the f64 difference-form d^2
+//     of every list entry (each term exact, summed in a fixed order) and selects rank k - c_i by a radix select over the bit patterns of the (non-negative)
+//     doubles: the value AT the rank, ties or not.  The approximate products never decide the rank and never supply the value.
 // No workgroup waits for another inside a kernel; the only atomics are integer adds (counts, list cursors).  Two calls give the same bits.
 #include "dic_exactd2.h"
-#include "dic_knn_count.h"          // KnTileArgs, KnCount: the counting epilogue, shared with dic_knn_rank.hip
+#include "dic_candlist.h"          // KnTileArgs, KnCount and the list protocol, shared with dic_knn_rank.hip
 #include "dic_pairtile.h"
 
 namespace dic {
@@ -35,13 +34,11 @@ namespace dic {
 constexpr int KN_T = 16;                               // thresholds per row and refining pass
 constexpr int KN_REFINE = 3;                           // refining passes
 constexpr int KN_ENTRY = 12;                           // bytes of candidate storage per list entry: int32 index + f64 d^2
-constexpr long long KN_DEFAULT_BUDGET = 384LL << 20;   // bytes (list sizes at 75 000 x 256)
 
 struct KnLayout { size_t thr, cnt, lo, hi, bnd, off, cursor, bounds, plan, idx, d2, total; long long entries; };
-struct KnPlan { long long total, longest, groups; int flag; };          // device words the host reads back
 
 static long long kn_entries(int64_t N, int64_t budget) {
-    if (budget <= 0) budget = KN_DEFAULT_BUDGET;
+    if (budget <= 0) budget = CL_DEFAULT_BUDGET;
     const long long all = (long long)N * N;          // every pair a candidate: nothing larger is ever needed
     return max(1LL, min((long long)(budget / KN_ENTRY), all));
 }
@@ -63,17 +60,6 @@ static KnLayout kn_layout(int64_t N, int64_t budget) {
     o.d2 = o.idx + align_up((size_t)o.entries * sizeof(int32_t), 256);
     o.total = o.d2 + align_up((size_t)o.entries * sizeof(double), 256);
     return o;
-}
-
-// nmax = the largest norm (one workgroup over the block maxima)
-__global__ __launch_bounds__(256) void kn_gmax_kernel(const float* bmax, int nblk, float* gmax) {
-    __shared__ float part[4];
-    float v = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += 256) v = fmaxf(v, bmax[i]);
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) *gmax = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
 }
 
 __device__ __forceinline__ void kn_spread(float lo, float hi, float* thr) {
@@ -114,66 +100,15 @@ __global__ __launch_bounds__(256) void kn_bracket_kernel(int n, int k, float* lo
     kn_spread(l, h, thr + (size_t)i * KN_T);
 }
 
-// the window (wlo, whi) of every row, at stride 2 (a launch of its own: it overwrites the refining thresholds of other rows)
+// The window (wlo, whi] of every row, at stride 2 (a launch of its own: it overwrites the refining thresholds of other rows).  The k-th distance takes the
+// candidates around the bracket, wlo = lo - 2.01 B; a neighbour LIST takes everything up to whi (wlo = -inf: c_i = 0).
+template <bool LISTS>
 __global__ __launch_bounds__(256) void kn_window_kernel(int n, const float* lo, const float* hi, const float* bnd, float* thr) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const float m = 2.01f * bnd[i];
-    thr[(size_t)i * 2] = lo[i] - m;
+    thr[(size_t)i * 2] = LISTS ? -__builtin_inff() : lo[i] - m;
     thr[(size_t)i * 2 + 1] = hi[i] + m;
-}
-
-// List lengths -> off[0..n] (exclusive prefix sum: row i's list is entries off[i] - off[r0] .. of its group's buffer), their total and the longest.
-// One workgroup; thread t owns a contiguous run of rows.
-__global__ __launch_bounds__(1024) void kn_scan_kernel(const int32_t* cnt, int n, long long* off, KnPlan* plan) {
-    __shared__ long long part[1024], longest[1024];
-    const int tid = threadIdx.x;
-    const int per = (n + 1023) / 1024, b = min(n, tid * per), e = min(n, b + per);
-    long long s = 0, m = 0;
-    for (int i = b; i < e; ++i) {
-        const long long len = (long long)cnt[(size_t)i * 2 + 1] - cnt[(size_t)i * 2];
-        s += len;
-        m = max(m, len);
-    }
-    part[tid] = s; longest[tid] = m;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0, mm = 0;
-        for (int t = 0; t < 1024; ++t) {
-            const long long v = part[t];
-            part[t] = run;
-            run += v;
-            mm = max(mm, longest[t]);
-        }
-        off[n] = run;
-        plan->total = run; plan->longest = mm; plan->groups = 0; plan->flag = 0;
-    }
-    __syncthreads();
-    s = part[tid];
-    for (int i = b; i < e; ++i) {
-        off[i] = s;
-        s += (long long)cnt[(size_t)i * 2 + 1] - cnt[(size_t)i * 2];
-    }
-}
-
-// The groups: consecutive rows, as many as fit `entries` list entries (no list is longer than that: checked by the host before this runs).
-// bounds[g] = first row of group g, bounds[groups] = n.
-__global__ void kn_groups_kernel(const long long* off, int n, long long entries, int32_t* bounds, KnPlan* plan) {
-    if (threadIdx.x || blockIdx.x) return;
-    int g = 0, r = 0;
-    while (r < n) {
-        bounds[g++] = r;
-        const long long lim = off[r] + entries;
-        int a = r + 1, b = n;          // the largest e in [r + 1, n] with off[e] <= lim  (off[r + 1] <= lim holds)
-        while (a < b) {
-            const int mid = (a + b + 1) / 2;
-            if (off[mid] <= lim) a = mid;
-            else b = mid - 1;
-        }
-        r = a;
-    }
-    bounds[g] = n;
-    plan->groups = g;
 }
 
 // Gather epilogue: rows r0 <= i < r1 append every j with wlo_i < a_ij <= whi_i to their list.
@@ -227,16 +162,32 @@ __global__ __launch_bounds__(512, 1) void kn_gather_kernel(KnTileArgs a) {
     pt_pair_pass(a.p, epi);
 }
 
-// One workgroup per row of the group: the exact d^2 of every list entry (one wave per entry: dic_exactd2.h -- lane l holds coordinates 4 l .. 4 l + 3, f64
-// difference form, fixed summation order; dic_optics.hip computes its distances with the same function), then the value at rank k - c_i by a radix select over the doubles' bit patterns (non-negative: unsigned order = numeric order),
-// eight 8-bit digits from the top.  kth[i] = its square root.  plan->flag is set if a row's rank falls outside its list or a list slot holds no point (the
-// invariants say neither can happen).
+// What both exact kernels open with: d2[o + e] = the exact d^2 of xi and list entry e, e < len (one wave per entry: dic_exactd2.h -- lane l holds coordinates
+// 4 l .. 4 l + 3, f64 difference form, fixed summation order; dic_optics.hip computes its distances with the same function).  A slot the gather pass did not
+// fill (it fills every one) is reported and read as point `stand_in`, to stay inside X.
+__device__ __forceinline__ void kn_list_d2(const float* X, long ldx, int d, int n, const ed_f32x4 xi, int stand_in, const int32_t* idx, double* d2, long long o,
+                                           int len, ClPlan* plan) {
+    const int lane = threadIdx.x & 63;
+    for (int e = threadIdx.x >> 6; e < len; e += 4) {
+        int j = idx[o + e];
+        if ((unsigned)j >= (unsigned)n) {
+            if (lane == 0) plan->flag = 1;
+            j = stand_in;
+        }
+        const double s = exact_d2(xi, exact_d2_load(X, ldx, (size_t)j, d));
+        if (lane == 0) d2[o + e] = s;
+    }
+}
+
+// One workgroup per row of the group: the exact d^2 of every list entry, then the value at rank k - c_i by a radix select over the doubles' bit patterns
+// (non-negative: unsigned order = numeric order), eight 8-bit digits from the top.  kth[i] = its square root.  plan->flag is set if a row's rank falls
+// outside its list or a list slot holds no point (the invariants say neither can happen).
 __global__ __launch_bounds__(256) void kn_exact_kernel(const float* X, long ldx, int d, int n, int r0, int k, const int32_t* cnt, const long long* off,
-                                                       const int32_t* idx, double* d2, long long entries, double* kth, KnPlan* plan) {
+                                                       const int32_t* idx, double* d2, long long entries, double* kth, ClPlan* plan) {
     __shared__ unsigned hist[256];
     __shared__ unsigned long long sel_prefix;
     __shared__ int sel_rank;
-    const int i = r0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int i = r0 + blockIdx.x, tid = threadIdx.x;
     const int c = cnt[(size_t)i * 2], len = cnt[(size_t)i * 2 + 1] - c;
     const long long o = off[i] - off[r0];
     int rank = k - c;          // 1-based, within the list
@@ -247,16 +198,7 @@ __global__ __launch_bounds__(256) void kn_exact_kernel(const float* X, long ldx,
         }
         return;
     }
-    const ed_f32x4 xi = exact_d2_load(X, ldx, (size_t)i, d);
-    for (int e = w; e < len; e += 4) {
-        int j = idx[o + e];
-        if ((unsigned)j >= (unsigned)n) {          // a slot the gather pass did not fill (it fills every one): stay inside X and report
-            if (lane == 0) plan->flag = 1;
-            j = i;
-        }
-        const double s = exact_d2(xi, exact_d2_load(X, ldx, (size_t)j, d));
-        if (lane == 0) d2[o + e] = s;
-    }
+    kn_list_d2(X, ldx, d, n, exact_d2_load(X, ldx, (size_t)i, d), i, idx, d2, o, len, plan);
     __syncthreads();
     unsigned long long prefix = 0;
     for (int shift = 56; shift >= 0; shift -= 8) {
@@ -300,25 +242,11 @@ __global__ __launch_bounds__(256) void kn_exact_kernel(const float* X, long ldx,
 //     bank conflicts; the last, neighbours 16 B apart, is 2-way), and the row written.  The order the gather filled the list in cannot matter.
 constexpr int KN_MAXK = 1024;
 
-// queries (and the padding behind them) as operand j: rows first .. first + count - 1 of pb present the norm pad_norm
-__global__ __launch_bounds__(256) void knl_mask_cols_kernel(__bf16* pb, long long first, long long count, float pad_norm) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t < count) pb[(size_t)(first + t) * PT_LD + PT_D + 3] = (__bf16)pad_norm;
-}
-
-// the list window of every row, at stride 2: everything up to whi
-__global__ __launch_bounds__(256) void knl_window_kernel(int n, const float* hi, const float* bnd, float* thr) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    thr[(size_t)i * 2] = -__builtin_inff();
-    thr[(size_t)i * 2 + 1] = hi[i] + 2.01f * bnd[i];
-}
-
 // One workgroup per row r0 + blockIdx.x of the stacked set (row `first` = query 0 = output row 0).  plan->flag is set if a list is shorter than k, a slot
 // holds no index point or the select does not leave exactly k entries (the invariants say none can happen); the row is then NaN / -1.
 __global__ __launch_bounds__(256) void knl_exact_kernel(const float* X, long ldx, const float* Q, long ldq, int d, int n, int first, int r0, int k,
                                                         const int32_t* cnt, const long long* off, const int32_t* idx, double* d2, long long entries,
-                                                        double* dist, int32_t* nbr, KnPlan* plan) {
+                                                        double* dist, int32_t* nbr, ClPlan* plan) {
     __shared__ unsigned long long sk[KN_MAXK];
     __shared__ int sj[KN_MAXK];
     __shared__ unsigned hist[256];
@@ -334,16 +262,7 @@ __global__ __launch_bounds__(256) void knl_exact_kernel(const float* X, long ldx
         for (int r = tid; r < k; r += 256) { drow[r] = __builtin_nan(""); jrow[r] = -1; }
         return;
     }
-    const ed_f32x4 xi = Q ? exact_d2_load(Q, ldq, (size_t)(i - first), d) : exact_d2_load(X, ldx, (size_t)i, d);
-    for (int e = w; e < len; e += 4) {
-        int j = idx[o + e];
-        if ((unsigned)j >= (unsigned)n) {          // a slot the gather pass did not fill (it fills every one): stay inside X and report
-            if (lane == 0) plan->flag = 1;
-            j = 0;
-        }
-        const double s = exact_d2(xi, exact_d2_load(X, ldx, (size_t)j, d));
-        if (lane == 0) d2[o + e] = s;
-    }
+    kn_list_d2(X, ldx, d, n, Q ? exact_d2_load(Q, ldq, (size_t)(i - first), d) : exact_d2_load(X, ldx, (size_t)i, d), 0, idx, d2, o, len, plan);
     if (tid == 0) filled = 0;
     __syncthreads();
     // the key (pd, pj) of rank k: twelve 8-bit digits from the top, eight of the double's bit pattern (non-negative: unsigned order = numeric order), four of j
@@ -451,7 +370,7 @@ static int knl_prepare_planes(const float* X, long ldx, int64_t N, const float* 
     if (M > 0)
         hipLaunchKernelGGL(pt_prep_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, Q, ldq, centre, (int)M, D, pa + (size_t)N * PT_LD, pb + (size_t)N * PT_LD,
                            plane, nrm + N);
-    hipLaunchKernelGGL(knl_mask_cols_kernel, dim3((unsigned)((M + PT_T + 255) / 256)), dim3(256), 0, st, pb, (long long)N, (long long)(M + PT_T), PT_PAD_NORM);
+    hipLaunchKernelGGL(pt_mask_cols_kernel, dim3((unsigned)((M + PT_T + 255) / 256)), dim3(256), 0, st, pb, (long long)N, (long long)(M + PT_T), PT_PAD_NORM);
     hipLaunchKernelGGL(pt_block_max_kernel, dim3((unsigned)((P + PT_T - 1) / PT_T)), dim3(256), 0, st, (const float*)nrm, (int)P, (float*)(ws + o.bmax));
     return DIC_OK;
 }
@@ -459,6 +378,48 @@ static int knl_prepare_planes(const float* X, long ldx, int64_t N, const float* 
 static int kn_reserve_lds() {
     static bool done = false;
     return pt_reserve_lds(done, {(const void*)kn_count_kernel<KN_T>, (const void*)kn_count_kernel<2>, (const void*)kn_gather_kernel}, "knn");
+}
+
+// Everything behind the planes, for both entry points, on the P rows of a kn_layout(P) workspace whose planes are filled and whose t.p walks the tiles to
+// count: the brackets (1) of the walked rows [rb, P) (whole row blocks), the window (2) of the kind LISTS, and (3) for the listed rows [first, P), rb <=
+// first, with the caller's exact kernel enqueued by exact(r0, r1) behind each group's gather pass.  The k-th distance is rb = first = 0.
+template <bool LISTS, class Exact>
+static int kn_select(KnTileArgs& t, unsigned char* ws, const KnLayout& o, int64_t P, int rb, int first, int k, int64_t* stats, hipStream_t st,
+                     const ClNames& nm, Exact&& exact) {
+    const int nr = (int)(P - rb), nq = (int)(P - first);
+    float* thr = (float*)(ws + o.thr);
+    int32_t* cnt = (int32_t*)(ws + o.cnt);
+    float* lo = (float*)(ws + o.lo) + rb;
+    float* hi = (float*)(ws + o.hi) + rb;
+    float* bnd = (float*)(ws + o.bnd) + rb;
+    long long* off = (long long*)(ws + o.off);
+    int32_t* cursor = (int32_t*)(ws + o.cursor);
+    ClPlan* plan = (ClPlan*)(ws + o.plan);
+    float* gmax = (float*)(ws + pt_layout(P).count);
+    t.thr = thr; t.cnt = cnt; t.off = off; t.cursor = cursor; t.idx = (int32_t*)(ws + o.idx); t.entries = o.entries;
+    const dim3 rows((unsigned)((nr + 255) / 256)), tgrid(pt_grid(t.p.ntiles)), tblk(512);
+    // the padding rows' thresholds and window are read (and masked): defined values
+    hipError_t e = hipMemsetAsync(thr + (size_t)P * KN_T, 0, (size_t)PT_T * KN_T * sizeof(float), st);
+    if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, (size_t)P * sizeof(int32_t), st);
+    // the refining passes zero the counts of the walked rows at stride KN_T, [KN_T rb, KN_T P); the last pass counts at stride 2, [2 rb, 2 P), which lies
+    // below that range when the walk does not start at row 0: zero all of it
+    if (e == hipSuccess && rb > 0) e = hipMemsetAsync(cnt, 0, (size_t)P * KN_T * sizeof(int32_t), st);
+    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "%s: memset: %s", nm.who, hipGetErrorString(e));
+    hipLaunchKernelGGL(cl_gmax_kernel, dim3(1), dim3(256), 0, st, t.p.bmax, (int)((P + PT_T - 1) / PT_T), gmax);
+    hipLaunchKernelGGL(kn_init_kernel, rows, dim3(256), 0, st, t.p.nrm + rb, (const float*)gmax, nr, lo, hi, bnd, thr + (size_t)rb * KN_T, cnt + (size_t)rb * KN_T);
+    for (int p = 0; p < KN_REFINE; ++p) {
+        hipLaunchKernelGGL((kn_count_kernel<KN_T>), tgrid, tblk, PT_LDS, st, t);
+        hipLaunchKernelGGL(kn_bracket_kernel, rows, dim3(256), 0, st, nr, k, lo, hi, thr + (size_t)rb * KN_T, cnt + (size_t)rb * KN_T);
+    }
+    hipLaunchKernelGGL((kn_window_kernel<LISTS>), rows, dim3(256), 0, st, nr, (const float*)lo, (const float*)hi, (const float*)bnd, thr + (size_t)rb * 2);
+    hipLaunchKernelGGL((kn_count_kernel<2>), tgrid, tblk, PT_LDS, st, t);
+    hipLaunchKernelGGL((cl_scan_kernel<ClWindowLen>), dim3(1), dim3(1024), 0, st, ClWindowLen{cnt + (size_t)first * 2}, nq, off + first, plan);
+    return cl_run_groups(plan, off, (int32_t*)(ws + o.bounds), nq, first, o.entries, KN_ENTRY, stats, KN_REFINE + 1, st, nm, [&](int r0, int r1) {
+        t.r0 = r0; t.r1 = r1;
+        cl_walk_rows(t.p, r0, r1);
+        hipLaunchKernelGGL(kn_gather_kernel, dim3(pt_grid(t.p.ntiles)), tblk, PT_LDS, st, t);
+        exact(r0, r1);
+    });
 }
 
 }  // namespace dic
@@ -492,79 +453,11 @@ int dic_knn_kth_distance(const float* X, long ldx, const float* centre, int64_t 
     if (rc) return rc;
     KnTileArgs t{};
     pt_fill_pair_args(t.p, ws, N);
-    float* thr = (float*)(ws + o.thr);
-    int32_t* cnt = (int32_t*)(ws + o.cnt);
-    float* lo = (float*)(ws + o.lo);
-    float* hi = (float*)(ws + o.hi);
-    float* bnd = (float*)(ws + o.bnd);
-    long long* off = (long long*)(ws + o.off);
-    int32_t* cursor = (int32_t*)(ws + o.cursor);
-    int32_t* bounds = (int32_t*)(ws + o.bounds);
-    KnPlan* plan = (KnPlan*)(ws + o.plan);
-    float* gmax = (float*)(ws + pt_layout(N).count);
-    t.thr = thr; t.cnt = cnt; t.off = off; t.cursor = cursor; t.idx = (int32_t*)(ws + o.idx); t.entries = o.entries;
-    const int n = (int)N, kk = (int)k;
-    const dim3 rows((unsigned)((N + 255) / 256)), tgrid(pt_grid(t.p.ntiles)), tblk(512);
-    // the padding rows' thresholds and window are read (and masked): defined values
-    hipError_t e = hipMemsetAsync(thr + (size_t)N * KN_T, 0, (size_t)PT_T * KN_T * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, (size_t)N * sizeof(int32_t), st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_kth_distance: memset: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(kn_gmax_kernel, dim3(1), dim3(256), 0, st, t.p.bmax, t.p.nblk, gmax);
-    hipLaunchKernelGGL(kn_init_kernel, rows, dim3(256), 0, st, t.p.nrm, (const float*)gmax, n, lo, hi, bnd, thr, cnt);
-    for (int p = 0; p < KN_REFINE; ++p) {
-        hipLaunchKernelGGL((kn_count_kernel<KN_T>), tgrid, tblk, PT_LDS, st, t);
-        hipLaunchKernelGGL(kn_bracket_kernel, rows, dim3(256), 0, st, n, kk, lo, hi, thr, cnt);
-    }
-    hipLaunchKernelGGL(kn_window_kernel, rows, dim3(256), 0, st, n, (const float*)lo, (const float*)hi, (const float*)bnd, thr);
-    hipLaunchKernelGGL((kn_count_kernel<2>), tgrid, tblk, PT_LDS, st, t);
-    hipLaunchKernelGGL(kn_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t*)cnt, n, off, plan);
-    rc = check_launch("knn_kth_distance counting");
-    if (rc) return rc;
-    // the list lengths decide the groups: read their summary back (synchronises the stream)
-    KnPlan hp;
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_kth_distance: reading the list lengths: %s", hipGetErrorString(e));
-    if (stats) {
-        stats[0] = KN_REFINE + 1;
-        stats[1] = 0;
-        stats[2] = hp.longest;
-        stats[3] = hp.total;
-        stats[4] = hp.longest * KN_ENTRY;
-    }
-    DIC_REQUIRE(hp.longest <= o.entries, DIC_ERR_WORKSPACE, "knn_kth_distance: a row has %lld candidates (%lld bytes), candidate_budget holds %lld (%lld "
-                "bytes): run again with candidate_budget >= %lld", hp.longest, hp.longest * KN_ENTRY, o.entries, o.entries * KN_ENTRY, hp.longest * KN_ENTRY);
-    hipLaunchKernelGGL(kn_groups_kernel, dim3(1), dim3(64), 0, st, (const long long*)off, n, o.entries, bounds, plan);
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_kth_distance: reading the groups: %s", hipGetErrorString(e));
-    if (stats) stats[1] = hp.groups;
-    constexpr int CHUNK = 1024;          // group bounds come back this many at a time
-    int32_t hb[CHUNK + 1];
-    for (long long g0 = 0; g0 < hp.groups; g0 += CHUNK) {
-        const int ng = (int)min((long long)CHUNK, hp.groups - g0);
-        e = hipMemcpyAsync(hb, bounds + g0, (size_t)(ng + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_kth_distance: reading the groups: %s", hipGetErrorString(e));
-        for (int g = 0; g < ng; ++g) {
-            const int r0 = hb[g], r1 = hb[g + 1];
-            DIC_REQUIRE(r0 >= 0 && r0 < r1 && r1 <= n, DIC_ERR_LAUNCH, "knn_kth_distance: group %lld = rows [%d, %d)", g0 + g, r0, r1);
-            const int b0 = r0 / PT_T, b1 = (r1 + PT_T - 1) / PT_T;
-            t.r0 = r0; t.r1 = r1;
-            t.p.tile0 = (long long)b0 * t.p.nblk;
-            t.p.ntiles = (long long)(b1 - b0) * t.p.nblk;
-            hipLaunchKernelGGL(kn_gather_kernel, dim3(pt_grid(t.p.ntiles)), tblk, PT_LDS, st, t);
-            hipLaunchKernelGGL(kn_exact_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, X, ldx, D, n, r0, kk, (const int32_t*)cnt, (const long long*)off,
-                               (const int32_t*)t.idx, (double*)(ws + o.d2), o.entries, kth, plan);
-        }
-        rc = check_launch("knn_kth_distance gather");
-        if (rc) return rc;
-    }
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_kth_distance: %s", hipGetErrorString(e));
-    DIC_REQUIRE(hp.flag == 0, DIC_ERR_LAUNCH, "knn_kth_distance: a row's rank fell outside its candidate list or a list was incomplete (non-finite coordinates?)");
-    return DIC_OK;
+    const ClNames nm{"knn_kth_distance", "a row has", "candidates", "a row's rank fell outside its candidate list or a list was incomplete"};
+    return kn_select<false>(t, ws, o, N, 0, 0, (int)k, stats, st, nm, [&](int r0, int r1) {
+        hipLaunchKernelGGL(kn_exact_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, X, ldx, D, (int)N, r0, (int)k, (const int32_t*)t.cnt, t.off,
+                           (const int32_t*)t.idx, (double*)(ws + o.d2), o.entries, kth, (ClPlan*)(ws + o.plan));
+    });
 }
 
 size_t dic_knn_neighbors_workspace(int64_t N, int64_t M, int D, int64_t candidate_budget) {
@@ -593,93 +486,19 @@ int dic_knn_neighbors(const float* X, long ldx, int64_t N, const float* Q, long 
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     unsigned char* ws = (unsigned char*)workspace;
-    const PtLayout pl = pt_layout(P);
-    KnTileArgs t{};
-    pt_fill_pair_args(t.p, ws, P);
-    const int nblk = t.p.nblk;                                    // row blocks of the stacked set
     rc = knl_prepare_planes(X, ldx, N, Q, ldq, M, centre, D, ws, st);
     if (rc) return rc;
-    const int first = (int)(M > 0 ? N : 0), nq = (int)(P - first);          // the query rows [first, P)
-    const int b0 = first / PT_T, rb = b0 * PT_T, nr = (int)(P - rb);      // the rows of the walked blocks [rb, P): all of them get a bracket
-    t.p.nblk = (int)((N + PT_T - 1) / PT_T);                             // column blocks holding an index point
-    t.p.tile0 = (long long)b0 * t.p.nblk;
-    t.p.ntiles = (long long)(nblk - b0) * t.p.nblk;
-    float* thr = (float*)(ws + o.thr);
-    int32_t* cnt = (int32_t*)(ws + o.cnt);
-    float* lo = (float*)(ws + o.lo);
-    float* hi = (float*)(ws + o.hi);
-    float* bnd = (float*)(ws + o.bnd);
-    long long* off = (long long*)(ws + o.off);
-    int32_t* cursor = (int32_t*)(ws + o.cursor);
-    int32_t* bounds = (int32_t*)(ws + o.bounds);
-    KnPlan* plan = (KnPlan*)(ws + o.plan);
-    float* gmax = (float*)(ws + pl.count);
-    t.thr = thr; t.cnt = cnt; t.off = off; t.cursor = cursor; t.idx = (int32_t*)(ws + o.idx); t.entries = o.entries;
-    const dim3 rows((unsigned)((nr + 255) / 256)), tgrid(pt_grid(t.p.ntiles)), tblk(512);
-    // the padding rows' thresholds and window are read (and masked): defined values
-    hipError_t e = hipMemsetAsync(thr + (size_t)P * KN_T, 0, (size_t)PT_T * KN_T * sizeof(float), st);
-    if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, (size_t)P * sizeof(int32_t), st);
-    // the refining passes zero the counts of the walked rows at stride KN_T, [KN_T rb, KN_T P); the last pass counts at stride 2, [2 rb, 2 P), which lies
-    // below that range when the walk does not start at row 0: zero all of it
-    if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)P * KN_T * sizeof(int32_t), st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_neighbors: memset: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(kn_gmax_kernel, dim3(1), dim3(256), 0, st, t.p.bmax, nblk, gmax);
-    hipLaunchKernelGGL(kn_init_kernel, rows, dim3(256), 0, st, t.p.nrm + rb, (const float*)gmax, nr, lo + rb, hi + rb, bnd + rb, thr + (size_t)rb * KN_T,
-                       cnt + (size_t)rb * KN_T);
-    for (int p = 0; p < KN_REFINE; ++p) {
-        hipLaunchKernelGGL((kn_count_kernel<KN_T>), tgrid, tblk, PT_LDS, st, t);
-        hipLaunchKernelGGL(kn_bracket_kernel, rows, dim3(256), 0, st, nr, k, lo + rb, hi + rb, thr + (size_t)rb * KN_T, cnt + (size_t)rb * KN_T);
-    }
-    hipLaunchKernelGGL(knl_window_kernel, rows, dim3(256), 0, st, nr, (const float*)(hi + rb), (const float*)(bnd + rb), thr + (size_t)rb * 2);
-    hipLaunchKernelGGL((kn_count_kernel<2>), tgrid, tblk, PT_LDS, st, t);
-    hipLaunchKernelGGL(kn_scan_kernel, dim3(1), dim3(1024), 0, st, (const int32_t*)(cnt + (size_t)first * 2), nq, off + first, plan);
-    rc = check_launch("knn_neighbors counting");
-    if (rc) return rc;
-    // the list lengths decide the groups: read their summary back (synchronises the stream)
-    KnPlan hp;
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_neighbors: reading the list lengths: %s", hipGetErrorString(e));
-    if (stats) {
-        stats[0] = KN_REFINE + 1;
-        stats[1] = 0;
-        stats[2] = hp.longest;
-        stats[3] = hp.total;
-        stats[4] = hp.longest * KN_ENTRY;
-    }
-    DIC_REQUIRE(hp.longest <= o.entries, DIC_ERR_WORKSPACE, "knn_neighbors: a row's list has %lld entries (%lld bytes), candidate_budget holds %lld (%lld "
-                "bytes): run again with candidate_budget >= %lld", hp.longest, hp.longest * KN_ENTRY, o.entries, o.entries * KN_ENTRY, hp.longest * KN_ENTRY);
-    hipLaunchKernelGGL(kn_groups_kernel, dim3(1), dim3(64), 0, st, (const long long*)(off + first), nq, o.entries, bounds, plan);
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_neighbors: reading the groups: %s", hipGetErrorString(e));
-    if (stats) stats[1] = hp.groups;
-    constexpr int CHUNK = 1024;          // group bounds (relative to the first query row) come back this many at a time
-    int32_t hb[CHUNK + 1];
-    for (long long g0 = 0; g0 < hp.groups; g0 += CHUNK) {
-        const int ng = (int)min((long long)CHUNK, hp.groups - g0);
-        e = hipMemcpyAsync(hb, bounds + g0, (size_t)(ng + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_neighbors: reading the groups: %s", hipGetErrorString(e));
-        for (int g = 0; g < ng; ++g) {
-            DIC_REQUIRE(hb[g] >= 0 && hb[g] < hb[g + 1] && hb[g + 1] <= nq, DIC_ERR_LAUNCH, "knn_neighbors: group %lld = queries [%d, %d)", g0 + g, hb[g], hb[g + 1]);
-            const int r0 = first + hb[g], r1 = first + hb[g + 1];
-            const int g0b = r0 / PT_T, g1b = (r1 + PT_T - 1) / PT_T;
-            t.r0 = r0; t.r1 = r1;
-            t.p.tile0 = (long long)g0b * t.p.nblk;
-            t.p.ntiles = (long long)(g1b - g0b) * t.p.nblk;
-            hipLaunchKernelGGL(kn_gather_kernel, dim3(pt_grid(t.p.ntiles)), tblk, PT_LDS, st, t);
-            hipLaunchKernelGGL(knl_exact_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, X, ldx, Q, ldq, D, (int)N, first, r0, k, (const int32_t*)cnt,
-                               (const long long*)off, (const int32_t*)t.idx, (double*)(ws + o.d2), o.entries, dist, idx, plan);
-        }
-        rc = check_launch("knn_neighbors gather");
-        if (rc) return rc;
-    }
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_neighbors: %s", hipGetErrorString(e));
-    DIC_REQUIRE(hp.flag == 0, DIC_ERR_LAUNCH, "knn_neighbors: a row's list was shorter than k or incomplete (non-finite coordinates?)");
-    return DIC_OK;
+    KnTileArgs t{};
+    pt_fill_pair_args(t.p, ws, P);
+    const int first = (int)(M > 0 ? N : 0), rb = first / PT_T * PT_T;          // the query rows [first, P); the rows of their blocks [rb, P) all get a bracket
+    t.p.nblk = (int)((N + PT_T - 1) / PT_T);                                  // column blocks holding an index point
+    cl_walk_rows(t.p, rb, (int)P);
+    const ClNames nm{"knn_neighbors", "a row's list has", "entries", "a row's list was shorter than k or incomplete"};
+    return kn_select<true>(t, ws, o, P, rb, first, k, stats, st, nm, [&](int r0, int r1) {
+        hipLaunchKernelGGL(knl_exact_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, X, ldx, Q, ldq, D, (int)N, first, r0, k, (const int32_t*)t.cnt, t.off,
+                           (const int32_t*)t.idx, (double*)(ws + o.d2), o.entries, dist, idx, (ClPlan*)(ws + o.plan));
+    });
 }
 
 }  // extern "C"
+

@@ -1,7 +1,7 @@
 // Neighbour ranks (include/dic_hip.h, dic_knn_ranks): where does j stand among the neighbours of i, for a short list of targets j per row -- the counterpart
 // of dic_knn.hip, which returns the value at a given rank.   rank(i, j) = 1 + #{ l != i : (d^2(i, l), l) < (d^2(i, j), j) },  d^2 the f64 difference-form
 // squared distance of dic_exactd2.h; a target j == i or outside [0, N) has rank 0.  Nothing N x N is stored: the pairs are recomputed tile by tile on the
-// matrix cores (dic_pairtile.h) and COUNTED against per-row thresholds, the epilogue dic_knn.hip selects with (dic_knn_count.h).
+// matrix cores (dic_pairtile.h) and COUNTED against per-row thresholds, the epilogue dic_knn.hip selects with (dic_candlist.h).
 //
 // THE APPROXIMATE d^2 ONLY NARROWS.  a_il is the tile loop's split-bf16 value, a fixed function of (i, l), and |a_il - d^2_il| < B_i = 2^-12 (n_i + nmax) for
 // every l (dic_pairtile.h, dic_knn.hip).
@@ -14,11 +14,10 @@
 //       - lo < a_il <= hi: the BAND of the target -- the pairs only the exact stage can place.  The target's own pair lies in it (|a_ij - t| < B).
 // (2) COUNTING PASSES, one per 8 targets: KnCount<16> against the 16 thresholds (lo, hi) x 8 of every row; cnt[lo] = the pairs certainly before (the self pair
 //     among them: below) and cnt[hi] - cnt[lo] = the band's size.  Absent targets and the padding behind the last carry lo = hi = -inf: nothing counted.
-// (3) GATHER + EXACT over groups of rows sized by the candidate budget.  A row's list holds one (l, q) entry per band pair of each of its targets q: its
-//     length is the sum of the band sizes, known from (2); the offsets are their prefix sum, the slot inside a list comes from an integer atomic cursor, and no
-//     write goes past the counted length.  One gather pass per 8 targets walks the tiles of the group's row blocks.  The exact kernel, one workgroup per row,
-//     recomputes t of every target (the same function: the same bits), computes d^2(i, l) of every entry with l != i and adds 1 to the target's count where
-//     (d^2(i, l), l) < (t, j).
+// (3) GATHER + EXACT over groups of rows sized by the candidate budget (dic_candlist.h has the protocol, what the budget can change and the guards).  A row's
+//     list holds one (l, q) entry per band pair of each of its targets q: its length is the sum of the band sizes, known from (2).  One gather pass per 8
+//     targets walks the tiles of the group's row blocks.  The exact kernel, one workgroup per row, recomputes t of every target (the same function: the
+//     same bits), computes d^2(i, l) of every entry with l != i and adds 1 to the target's count where (d^2(i, l), l) < (t, j).
 //         rank = 1 + cnt[lo] - [lo is finite] + #{band entries before the target}.
 //     The approximate products never decide an order.  The order of a list cannot matter: every entry is judged alone.
 // THE SELF PAIR l = i is no neighbour, and it is taken out by its index, never by its distance (a duplicate of i at distance 0 stays in).  In a band it is an
@@ -29,7 +28,7 @@
 //     more than the band proper).  Either way no comparison of a_ii decides anything.
 // No workgroup waits for another inside a kernel; the only atomics are integer adds (counts, cursors, LDS tallies).  Two calls give the same bits.
 #include "dic_exactd2.h"
-#include "dic_knn_count.h"
+#include "dic_candlist.h"
 #include "dic_pairtile.h"
 
 namespace dic {
@@ -38,14 +37,12 @@ constexpr int KR_T = 16;                               // thresholds per row and
 constexpr int KR_Q = KR_T / 2;                         // 8 targets
 constexpr int KR_MAXM = 1023;                          // targets per row
 constexpr int KR_ENTRY = 8;                            // bytes per list entry: int32 l, int32 q
-constexpr long long KR_DEFAULT_BUDGET = 384LL << 20;   // bytes, as dic_knn.hip's
 
 struct KrLayout { size_t thr, cnt, bnd, len, off, cursor, bounds, plan, list, total; long long entries; int passes; };
-struct KrPlan { long long total, longest, groups; int flag; };          // device words the host reads back
 
 static KrLayout kr_layout(int64_t N, int m, int64_t budget) {
     KrLayout o;
-    if (budget <= 0) budget = KR_DEFAULT_BUDGET;
+    if (budget <= 0) budget = CL_DEFAULT_BUDGET;
     const size_t rows = (size_t)(N + PT_T);
     const long long all = N > 3000000 ? (1LL << 62) : (long long)N * N * m;          // every pair in every band: nothing larger is ever needed
     o.entries = max(1LL, min(min((long long)(budget / KR_ENTRY), all), (1LL << 31) - 1));          // (16 GiB of lists at the most)
@@ -61,17 +58,6 @@ static KrLayout kr_layout(int64_t N, int m, int64_t budget) {
     o.list = o.plan + 256;
     o.total = o.list + align_up((size_t)o.entries * KR_ENTRY, 256);
     return o;
-}
-
-// nmax = the largest norm (one workgroup over the block maxima)
-__global__ __launch_bounds__(256) void kr_gmax_kernel(const float* bmax, int nblk, float* gmax) {
-    __shared__ float part[4];
-    float v = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += 256) v = fmaxf(v, bmax[i]);
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) *gmax = fmaxf(fmaxf(part[0], part[1]), fmaxf(part[2], part[3]));
 }
 
 // b_i of every row
@@ -125,57 +111,6 @@ __global__ __launch_bounds__(256) void kr_len_kernel(const int32_t* cnt, int n, 
         for (int q = 0; q < KR_Q; ++q) s += (long long)c[2 * q + 1] - c[2 * q];
     }
     len[i] = s;
-}
-
-// off[0..n] = the exclusive prefix sum of the lengths, their total and the longest.  One workgroup; thread t owns a contiguous run of rows.
-__global__ __launch_bounds__(1024) void kr_scan_kernel(const long long* len, int n, long long* off, KrPlan* plan) {
-    __shared__ long long part[1024], longest[1024];
-    const int tid = threadIdx.x;
-    const int per = (n + 1023) / 1024, b = min(n, tid * per), e = min(n, b + per);
-    long long s = 0, m = 0;
-    for (int i = b; i < e; ++i) {
-        s += len[i];
-        m = max(m, len[i]);
-    }
-    part[tid] = s; longest[tid] = m;
-    __syncthreads();
-    if (tid == 0) {
-        long long run = 0, mm = 0;
-        for (int t = 0; t < 1024; ++t) {
-            const long long v = part[t];
-            part[t] = run;
-            run += v;
-            mm = max(mm, longest[t]);
-        }
-        off[n] = run;
-        plan->total = run; plan->longest = mm; plan->groups = 0; plan->flag = 0;
-    }
-    __syncthreads();
-    s = part[tid];
-    for (int i = b; i < e; ++i) {
-        off[i] = s;
-        s += len[i];
-    }
-}
-
-// The groups: consecutive rows, as many as fit `entries` list entries (no list is longer: checked by the host before this runs).  Rows without entries
-// cost nothing, so a group may be long.  bounds[g] = first row of group g, bounds[groups] = n.
-__global__ void kr_groups_kernel(const long long* off, int n, long long entries, int32_t* bounds, KrPlan* plan) {
-    if (threadIdx.x || blockIdx.x) return;
-    int g = 0, r = 0;
-    while (r < n) {
-        bounds[g++] = r;
-        const long long lim = off[r] + entries;
-        int a = r + 1, b = n;          // the largest e in [r + 1, n] with off[e] <= lim  (off[r + 1] <= lim holds)
-        while (a < b) {
-            const int mid = (a + b + 1) / 2;
-            if (off[mid] <= lim) a = mid;
-            else b = mid - 1;
-        }
-        r = a;
-    }
-    bounds[g] = n;
-    plan->groups = g;
 }
 
 struct KrEntry { int32_t l, q; };
@@ -242,7 +177,7 @@ __global__ __launch_bounds__(512, 1) void kr_gather_kernel(KrGatherArgs a) {
 // cursor disagrees with the counted length or an entry names no point or no target (the invariants say none can happen).
 __global__ __launch_bounds__(256) void kr_exact_kernel(const float* X, long ldx, int d, int n, int r0, const int32_t* targets, int m, const float* thr,
                                                        const int32_t* cnt, const long long* off, const int32_t* cursor,
-                                                       const KrEntry* list, long long entries, int32_t* ranks, KrPlan* plan) {
+                                                       const KrEntry* list, long long entries, int32_t* ranks, ClPlan* plan) {
     __shared__ double st[KR_MAXM + 1];
     __shared__ int sj[KR_MAXM + 1], tally[KR_MAXM + 1];
     const int i = r0 + blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -323,7 +258,7 @@ int dic_knn_ranks(const float* X, long ldx, const float* centre, int64_t N, int 
     long long* off = (long long*)(ws + o.off);
     int32_t* cursor = (int32_t*)(ws + o.cursor);
     int32_t* bounds = (int32_t*)(ws + o.bounds);
-    KrPlan* plan = (KrPlan*)(ws + o.plan);
+    ClPlan* plan = (ClPlan*)(ws + o.plan);
     KrEntry* list = (KrEntry*)(ws + o.list);
     float* gmax = (float*)(ws + pt_layout(N).count);
     const int n = (int)N, P = o.passes;
@@ -333,7 +268,7 @@ int dic_knn_ranks(const float* X, long ldx, const float* centre, int64_t N, int 
     if (e == hipSuccess) e = hipMemsetAsync(cnt, 0, (size_t)P * rows * KR_T * sizeof(int32_t), st);
     if (e == hipSuccess) e = hipMemsetAsync(cursor, 0, rows * sizeof(int32_t), st);
     DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_ranks: memset: %s", hipGetErrorString(e));
-    hipLaunchKernelGGL(kr_gmax_kernel, dim3(1), dim3(256), 0, st, t.p.bmax, t.p.nblk, gmax);
+    hipLaunchKernelGGL(cl_gmax_kernel, dim3(1), dim3(256), 0, st, t.p.bmax, t.p.nblk, gmax);
     hipLaunchKernelGGL(kr_bound_kernel, rgrid, dim3(256), 0, st, t.p.nrm, (const float*)gmax, n, bnd);
     const long long waves = (long long)N * P * KR_Q;
     DIC_REQUIRE((waves + 3) / 4 < (1LL << 31), DIC_ERR_UNSUPPORTED, "knn_ranks: N=%lld x m=%d targets: too many for one launch", (long long)N, m);
@@ -344,60 +279,21 @@ int dic_knn_ranks(const float* X, long ldx, const float* centre, int64_t N, int 
         hipLaunchKernelGGL(kr_count_kernel, tgrid, tblk, PT_LDS, st, t);
     }
     hipLaunchKernelGGL(kr_len_kernel, rgrid, dim3(256), 0, st, (const int32_t*)cnt, n, P, len);
-    hipLaunchKernelGGL(kr_scan_kernel, dim3(1), dim3(1024), 0, st, (const long long*)len, n, off, plan);
-    rc = check_launch("knn_ranks counting");
-    if (rc) return rc;
-    // the list lengths decide the groups: read their summary back (synchronises the stream)
-    KrPlan hp;
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_ranks: reading the list lengths: %s", hipGetErrorString(e));
-    if (stats) {
-        stats[0] = P;
-        stats[2] = hp.longest;
-        stats[3] = hp.total;
-        stats[4] = hp.longest * KR_ENTRY;
-    }
-    DIC_REQUIRE(hp.longest <= o.entries, DIC_ERR_WORKSPACE, "knn_ranks: a row's bands hold %lld pairs (%lld bytes), candidate_budget holds %lld (%lld bytes): "
-                "run again with candidate_budget >= %lld", hp.longest, hp.longest * KR_ENTRY, o.entries, o.entries * KR_ENTRY, hp.longest * KR_ENTRY);
-    DIC_REQUIRE(hp.longest < (1LL << 31), DIC_ERR_UNSUPPORTED, "knn_ranks: a row's bands hold %lld pairs: fewer than 2^31", hp.longest);
-    hipLaunchKernelGGL(kr_groups_kernel, dim3(1), dim3(64), 0, st, (const long long*)off, n, o.entries, bounds, plan);
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_ranks: reading the groups: %s", hipGetErrorString(e));
-    if (stats) stats[1] = hp.groups;
+    hipLaunchKernelGGL((cl_scan_kernel<ClArrayLen>), dim3(1), dim3(1024), 0, st, ClArrayLen{len}, n, off, plan);
     KrGatherArgs g{};
     g.p = t.p; g.off = off; g.cursor = cursor; g.list = list; g.entries = (int)o.entries;
-    constexpr int CHUNK = 1024;          // group bounds come back this many at a time
-    int32_t hb[CHUNK + 1];
-    for (long long g0 = 0; g0 < hp.groups; g0 += CHUNK) {
-        const int ng = (int)min((long long)CHUNK, hp.groups - g0);
-        e = hipMemcpyAsync(hb, bounds + g0, (size_t)(ng + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_ranks: reading the groups: %s", hipGetErrorString(e));
-        for (int gg = 0; gg < ng; ++gg) {
-            const int r0 = hb[gg], r1 = hb[gg + 1];
-            DIC_REQUIRE(r0 >= 0 && r0 < r1 && r1 <= n, DIC_ERR_LAUNCH, "knn_ranks: group %lld = rows [%d, %d)", g0 + gg, r0, r1);
-            const int b0 = r0 / PT_T, b1 = (r1 + PT_T - 1) / PT_T;
-            g.r0 = r0; g.r1 = r1;
-            g.p.tile0 = (long long)b0 * g.p.nblk;
-            g.p.ntiles = (long long)(b1 - b0) * g.p.nblk;
-            for (int p = 0; p < P; ++p) {
-                g.thr = thr + (size_t)p * rows * KR_T;
-                g.q0 = p * KR_Q;
-                hipLaunchKernelGGL(kr_gather_kernel, dim3(pt_grid(g.p.ntiles)), tblk, PT_LDS, st, g);
-            }
-            hipLaunchKernelGGL(kr_exact_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, X, ldx, D, n, r0, targets, m, (const float*)thr, (const int32_t*)cnt,
-                               (const long long*)off, (const int32_t*)cursor, (const KrEntry*)list, o.entries, ranks, plan);
+    const ClNames nm{"knn_ranks", "a row's bands hold", "pairs", "a row's list was incomplete or held no point"};
+    return cl_run_groups(plan, off, bounds, n, 0, o.entries, KR_ENTRY, stats, P, st, nm, [&](int r0, int r1) {
+        g.r0 = r0; g.r1 = r1;
+        cl_walk_rows(g.p, r0, r1);
+        for (int p = 0; p < P; ++p) {
+            g.thr = thr + (size_t)p * rows * KR_T;
+            g.q0 = p * KR_Q;
+            hipLaunchKernelGGL(kr_gather_kernel, dim3(pt_grid(g.p.ntiles)), tblk, PT_LDS, st, g);
         }
-        rc = check_launch("knn_ranks gather");
-        if (rc) return rc;
-    }
-    e = hipMemcpyAsync(&hp, plan, sizeof(hp), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "knn_ranks: %s", hipGetErrorString(e));
-    DIC_REQUIRE(hp.flag == 0, DIC_ERR_LAUNCH, "knn_ranks: a row's list was incomplete or held no point (non-finite coordinates?)");
-    return DIC_OK;
+        hipLaunchKernelGGL(kr_exact_kernel, dim3((unsigned)(r1 - r0)), dim3(256), 0, st, X, ldx, D, n, r0, targets, m, (const float*)thr, (const int32_t*)cnt,
+                           (const long long*)off, (const int32_t*)cursor, (const KrEntry*)list, o.entries, ranks, plan);
+    });
 }
 
 }  // extern "C"

@@ -82,12 +82,6 @@ __device__ __forceinline__ double ms_d2(const ms_f64x4 s, const ms_f64x4 x) {
     return wave_sum(acc);
 }
 
-// rows first .. first + count - 1 of pb present the norm pad_norm as operand j (the rows between the last point and the first seed)
-__global__ __launch_bounds__(256) void ms_mask_cols_kernel(__bf16* pb, long long first, long long count, float pad_norm) {
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t < count) pb[(size_t)(first + t) * PT_LD + PT_D + 3] = (__bf16)pad_norm;
-}
-
 // pt_prep_kernel's row operand for f64 seeds: v = (float)(s - centre), the difference in f64, ONE rounding per coordinate.  One wave per seed.
 __global__ __launch_bounds__(256) void ms_seed_prep_kernel(const double* S, long lds, const float* mu, int m, int d, __bf16* pa, long plane, float* nrm_out) {
     const int lane = threadIdx.x & 63, row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -353,8 +347,8 @@ int dic_meanshift_prepare(const float* X, long ldx, int64_t N, int D, const floa
     if (e == hipSuccess) e = hipMemsetAsync(nrm + N, 0, (size_t)(o.rows + PT_T - N) * sizeof(float), st);
     DIC_REQUIRE(e == hipSuccess, DIC_ERR_LAUNCH, "meanshift_prepare: memset: %s", hipGetErrorString(e));
     hipLaunchKernelGGL(pt_prep_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, X, ldx, centre, (int)N, D, pa, pb, plane, nrm);
-    if (o.s0 > N)
-        hipLaunchKernelGGL(ms_mask_cols_kernel, dim3((unsigned)((o.s0 - N + 255) / 256)), dim3(256), 0, st, pb, (long long)N, (long long)(o.s0 - N), PT_PAD_NORM);
+    if (o.s0 > N)          // the rows between the last point and the first seed
+        hipLaunchKernelGGL(pt_mask_cols_kernel, dim3((unsigned)((o.s0 - N + 255) / 256)), dim3(256), 0, st, pb, (long long)N, (long long)(o.s0 - N), PT_PAD_NORM);
     hipLaunchKernelGGL(pt_block_max_kernel, dim3((unsigned)(o.s0 / PT_T)), dim3(256), 0, st, (const float*)nrm, (int)N, (float*)(ws + o.pt.bmax));
     return check_launch("meanshift_prepare");
 }

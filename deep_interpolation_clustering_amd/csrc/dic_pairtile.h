@@ -203,6 +203,14 @@ static __global__ __launch_bounds__(256) void pt_pad_rows_kernel(__bf16* pa, __b
     pb[et + 3] = (__bf16)pad_norm;
 }
 
+// Rows first .. first + count - 1 of pb present the norm pad_norm as operand j: rows behind the points that are no column of anybody's, as the padding
+// points are none (the queries dic_knn.hip stacks behind its index points to walk them as operand i; dic_meanshift.hip's rows between the last point and the
+// first seed).
+static __global__ __launch_bounds__(256) void pt_mask_cols_kernel(__bf16* pb, long long first, long long count, float pad_norm) {
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t < count) pb[(size_t)(first + t) * PT_LD + PT_D + 3] = (__bf16)pad_norm;
+}
+
 // Fills the planes, norms and block maxima of a pt_layout(N) workspace from X (N, D) f32 and the centre (1, D).  The 256 padding rows behind the last point,
 // which the last tiles read, are zero vectors of norm 0 as operand i (a_ij = n_j); as operand j they present the norm pad_norm, so their approximate d^2 is
 // n_i + pad_norm: with 0 an epilogue masks them by index, with a huge value they lie beyond every threshold and need no mask.  (The norm array and the block

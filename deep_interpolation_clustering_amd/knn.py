@@ -40,6 +40,23 @@ def _shape_of(X):
     return shape
 
 
+def _candidate_call(front, entry, candidate_budget, stats, run):
+    """What the three front ends of the candidate-list entry points end with: ``candidate_budget`` parsed (None: the library's default), ``run(budget, st)``
+    -- the caller's remaining checks, its allocations and its call of ``entry`` with the stats words ``st`` -- giving ``(rc, result)``; then ``stats``
+    filled, a list longer than the budget raised as ``CandidateBudgetError`` and any other failure through ``N.check``."""
+    budget = 0 if candidate_budget is None else int(candidate_budget)
+    if candidate_budget is not None and budget < 1:
+        raise ValueError('candidate_budget must be positive, got %r' % (candidate_budget,))
+    st = (N.C.c_int64 * len(STAT_NAMES))()
+    rc, result = run(budget, st)
+    if stats is not None:
+        stats.update(zip(STAT_NAMES, (int(v) for v in st)))
+    if rc == -3 and st[4] > 0:          # DIC_ERR_WORKSPACE: one list alone is longer than the budget
+        raise CandidateBudgetError('%s: %s' % (front, N.lib().dic_last_error_string().decode()), st[4])
+    N.check(rc, entry)
+    return result
+
+
 def kth_neighbor_distance(X, k, candidate_budget=None, stats=None):
     """(N,) float64 numpy: for every row of ``X`` (numpy array or tensor, (N, D), D <= 256) the k-th smallest euclidean distance to the rows of ``X``, itself
     included -- ``NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X)[0][:, -1]``, but exact for the f32 coordinates (f64 difference form).
@@ -51,25 +68,19 @@ def kth_neighbor_distance(X, k, candidate_budget=None, stats=None):
         raise ValueError('Expected n_neighbors > 0. Got %d' % k)
     if k > n:
         raise ValueError('Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %d' % (k, n))
-    budget = 0 if candidate_budget is None else int(candidate_budget)
-    if candidate_budget is not None and budget < 1:
-        raise ValueError('candidate_budget must be positive, got %r' % (candidate_budget,))
-    x = _device_points(X)
-    d = x.shape[1]
-    if d > MAX_DIM:
-        raise NotImplementedError('kth_neighbor_distance: at most %d features (got %d)' % (MAX_DIM, d))
-    L = N.lib()
-    ws = torch.empty(max(16, L.dic_knn_workspace(n, d, budget)), dtype=torch.uint8, device=x.device)
-    out = torch.empty(n, dtype=torch.float64, device=x.device)
-    centre = x.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
-    st = (N.C.c_int64 * len(STAT_NAMES))()
-    rc = L.dic_knn_kth_distance(N.ptr(x), x.stride(0), N.ptr(centre), n, d, k, N.ptr(out), budget, st, N.ptr(ws), ws.numel(), N.stream_of(x))
-    if stats is not None:
-        stats.update(zip(STAT_NAMES, (int(v) for v in st)))
-    if rc == -3 and st[4] > 0:          # DIC_ERR_WORKSPACE: one list alone is longer than the budget
-        raise CandidateBudgetError('kth_neighbor_distance: %s' % L.dic_last_error_string().decode(), st[4])
-    N.check(rc, 'dic_knn_kth_distance')
-    return out.cpu().numpy()
+
+    def run(budget, st):
+        x = _device_points(X)
+        d = x.shape[1]
+        if d > MAX_DIM:
+            raise NotImplementedError('kth_neighbor_distance: at most %d features (got %d)' % (MAX_DIM, d))
+        L = N.lib()
+        ws = torch.empty(max(16, L.dic_knn_workspace(n, d, budget)), dtype=torch.uint8, device=x.device)
+        out = torch.empty(n, dtype=torch.float64, device=x.device)
+        centre = x.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
+        return L.dic_knn_kth_distance(N.ptr(x), x.stride(0), N.ptr(centre), n, d, k, N.ptr(out), budget, st, N.ptr(ws), ws.numel(), N.stream_of(x)), out
+
+    return _candidate_call('kth_neighbor_distance', 'dic_knn_kth_distance', candidate_budget, stats, run).cpu().numpy()
 
 
 MAX_NEIGHBORS = 1024          # csrc/dic_knn.hip: KN_MAXK, the rows the exact stage sorts in LDS
@@ -104,29 +115,24 @@ def kneighbors(X, k, Q=None, candidate_budget=None, stats=None, return_device=Fa
         raise ValueError('Found array with 0 sample(s) (shape=(%d, %d)) while a minimum of 1 is required.' % (min(n, m), dx))
     k = int(k)
     _check_k(k, n, m)
-    budget = 0 if candidate_budget is None else int(candidate_budget)
-    if candidate_budget is not None and budget < 1:
-        raise ValueError('candidate_budget must be positive, got %r' % (candidate_budget,))
-    if dx > MAX_DIM:
-        raise NotImplementedError('kneighbors: at most %d features (got %d)' % (MAX_DIM, dx))
-    x = _device_points(X)
-    q = None
-    if Q is not None:
-        q = _device_points(Q).to(x.device)
-    d = x.shape[1]
-    L = N.lib()
-    ws = torch.empty(max(16, L.dic_knn_neighbors_workspace(n, 0 if q is None else m, d, budget)), dtype=torch.uint8, device=x.device)
-    dist = torch.empty((m, k), dtype=torch.float64, device=x.device)
-    idx = torch.empty((m, k), dtype=torch.int32, device=x.device)
-    centre = x.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
-    st = (N.C.c_int64 * len(STAT_NAMES))()
-    rc = L.dic_knn_neighbors(N.ptr(x), x.stride(0), n, None if q is None else N.ptr(q), 0 if q is None else q.stride(0), 0 if q is None else m, N.ptr(centre), d,
-                             k, N.ptr(dist), N.ptr(idx), budget, st, N.ptr(ws), ws.numel(), N.stream_of(x))
-    if stats is not None:
-        stats.update(zip(STAT_NAMES, (int(v) for v in st)))
-    if rc == -3 and st[4] > 0:          # DIC_ERR_WORKSPACE: one list alone is longer than the budget
-        raise CandidateBudgetError('kneighbors: %s' % L.dic_last_error_string().decode(), st[4])
-    N.check(rc, 'dic_knn_neighbors')
+
+    def run(budget, st):
+        if dx > MAX_DIM:
+            raise NotImplementedError('kneighbors: at most %d features (got %d)' % (MAX_DIM, dx))
+        x = _device_points(X)
+        q = None
+        if Q is not None:
+            q = _device_points(Q).to(x.device)
+        d = x.shape[1]
+        L = N.lib()
+        ws = torch.empty(max(16, L.dic_knn_neighbors_workspace(n, 0 if q is None else m, d, budget)), dtype=torch.uint8, device=x.device)
+        dist = torch.empty((m, k), dtype=torch.float64, device=x.device)
+        idx = torch.empty((m, k), dtype=torch.int32, device=x.device)
+        centre = x.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
+        return L.dic_knn_neighbors(N.ptr(x), x.stride(0), n, None if q is None else N.ptr(q), 0 if q is None else q.stride(0), 0 if q is None else m,
+                                   N.ptr(centre), d, k, N.ptr(dist), N.ptr(idx), budget, st, N.ptr(ws), ws.numel(), N.stream_of(x)), (dist, idx)
+
+    dist, idx = _candidate_call('kneighbors', 'dic_knn_neighbors', candidate_budget, stats, run)
     if return_device:
         return dist, idx
     return dist.cpu().numpy(), idx.cpu().numpy()
@@ -156,31 +162,26 @@ def neighbor_ranks(X, targets, candidate_budget=None, stats=None, return_device=
         raise ValueError('Expected n_targets > 0. Got %d' % m)
     if m > MAX_TARGETS:
         raise NotImplementedError('neighbor_ranks: at most %d targets per row (got %d)' % (MAX_TARGETS, m))
-    budget = 0 if candidate_budget is None else int(candidate_budget)
-    if candidate_budget is not None and budget < 1:
-        raise ValueError('candidate_budget must be positive, got %r' % (candidate_budget,))
-    if dx > MAX_DIM:
-        raise NotImplementedError('neighbor_ranks: at most %d features (got %d)' % (MAX_DIM, dx))
-    tt = torch.as_tensor(targets)
-    if tt.dtype.is_floating_point or tt.dtype == torch.bool or tt.dtype.is_complex:
-        raise ValueError('targets must be integers, got %s' % (tt.dtype,))
-    x = _device_points(X)
-    tt = tt.to(x.device)
-    if int(tt.max()) >= n:
-        raise ValueError('targets must be below n_samples = %d (negative: absent), got %d' % (n, int(tt.max())))
-    tt = tt.clamp(min=-1).to(torch.int32).contiguous()
-    d = x.shape[1]
-    L = N.lib()
-    ws = torch.empty(max(16, L.dic_knn_ranks_workspace(n, d, m, budget)), dtype=torch.uint8, device=x.device)
-    ranks = torch.empty((n, m), dtype=torch.int32, device=x.device)
-    centre = x.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
-    st = (N.C.c_int64 * len(STAT_NAMES))()
-    rc = L.dic_knn_ranks(N.ptr(x), x.stride(0), N.ptr(centre), n, d, N.ptr(tt), m, N.ptr(ranks), budget, st, N.ptr(ws), ws.numel(), N.stream_of(x))
-    if stats is not None:
-        stats.update(zip(STAT_NAMES, (int(v) for v in st)))
-    if rc == -3 and st[4] > 0:          # DIC_ERR_WORKSPACE: one row's bands alone are longer than the budget
-        raise CandidateBudgetError('neighbor_ranks: %s' % L.dic_last_error_string().decode(), st[4])
-    N.check(rc, 'dic_knn_ranks')
+
+    def run(budget, st):
+        if dx > MAX_DIM:
+            raise NotImplementedError('neighbor_ranks: at most %d features (got %d)' % (MAX_DIM, dx))
+        tt = torch.as_tensor(targets)
+        if tt.dtype.is_floating_point or tt.dtype == torch.bool or tt.dtype.is_complex:
+            raise ValueError('targets must be integers, got %s' % (tt.dtype,))
+        x = _device_points(X)
+        tt = tt.to(x.device)
+        if int(tt.max()) >= n:
+            raise ValueError('targets must be below n_samples = %d (negative: absent), got %d' % (n, int(tt.max())))
+        tt = tt.clamp(min=-1).to(torch.int32).contiguous()
+        d = x.shape[1]
+        L = N.lib()
+        ws = torch.empty(max(16, L.dic_knn_ranks_workspace(n, d, m, budget)), dtype=torch.uint8, device=x.device)
+        ranks = torch.empty((n, m), dtype=torch.int32, device=x.device)
+        centre = x.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
+        return L.dic_knn_ranks(N.ptr(x), x.stride(0), N.ptr(centre), n, d, N.ptr(tt), m, N.ptr(ranks), budget, st, N.ptr(ws), ws.numel(), N.stream_of(x)), ranks
+
+    ranks = _candidate_call('neighbor_ranks', 'dic_knn_ranks', candidate_budget, stats, run)
     return ranks if return_device else ranks.cpu().numpy()
 
 

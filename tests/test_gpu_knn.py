@@ -192,6 +192,35 @@ def test_budget_below_one_list_reports_the_size_needed():
     assert rc == -3 and st[4] == s0['budget_needed'] and st[2] == s0['max_list']
 
 
+@pytest.fixture(scope='module')
+def candlist_rec():
+    """scripts/record_knn_candlist_golden.py: the cases' inputs and how a run is reduced to what the fixture holds."""
+    import runpy
+    from types import SimpleNamespace
+    return SimpleNamespace(**runpy.run_path(os.path.join(os.path.dirname(os.path.abspath(__file__)), os.pardir, 'scripts', 'record_knn_candlist_golden.py')))
+
+
+CANDLIST_CASES = [('kth', 1537, 0, 20, 7), ('kth', 5, 0, 4, 5), ('lists', 700, 0, 36, 5), ('lists', 600, 300, 8, 4), ('lists', 256, 1, 4, 256),
+                  ('ranks', 513, 0, 12, 9), ('ranks', 300, 0, 8, 1)]
+
+
+@pytest.mark.parametrize('kind,n,m,d,k', CANDLIST_CASES)
+def test_candidate_list_driver_equals_the_recorded_bits(candlist_rec, kind, n, m, d, k):
+    """The k-th distances, the neighbour lists and the neighbour ranks against tests/golden/knn_candlist_parent.npz, BIT for bit (SHA-256 of the output
+    bytes) and in all five stats words: what the last commit with three copies of the list protocol computed on an MI355X
+    (scripts/record_knn_candlist_golden.py).  Each case at the default budget and at candidate_budget = budget_needed, the smallest legal one (the most
+    groups).  k-th distance: 7 row blocks with a partial last one, and N = k = 5.  Lists: the self join; queries whose first row is no block boundary (the
+    walk starts before the first listed row); a query block that starts at a boundary, k = N.  Ranks: two counting passes with absent and self targets and a
+    last block of one row; one target."""
+    assert (kind, n, m, d, k) in candlist_rec.CASES
+    golden = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'knn_candlist_parent.npz'))
+    got = candlist_rec.run_case(knn, kind, n, m, d, k)
+    assert len(got) == 2
+    for name, value in got.items():
+        print(name, value.tolist() if name.endswith('_stats') else '')
+        assert value.dtype == golden[name].dtype and np.array_equal(value, golden[name]), name
+
+
 def test_two_calls_are_bit_identical_and_core_distances_is_the_same_quantity():
     X = blobs(4000, 24, 5, 0.2, 0.15, seed=17)
     a = kth_neighbor_distance(X, 25)

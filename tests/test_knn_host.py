@@ -123,6 +123,33 @@ def test_workspace_is_monotone(lib):
     assert lib.dic_knn_workspace(75000, 256, 12) < 75000 * 75000 * 4 // 100
 
 
+# (N, M, D, m, candidate_budget): (dic_knn_workspace(N, D, b), dic_knn_neighbors_workspace(N, M, D, b), dic_knn_ranks_workspace(N, D, m, b)), as the library
+# computed them before the three entry points moved onto the shared candidate-list driver (csrc/dic_candlist.h).
+WORKSPACES_BEFORE_CANDLIST = {
+    (1, 0, 4, 1, 0): (636928, 636928, 636416),
+    (1, 1, 4, 1, 1): (636928, 638976, 636416),                          # a budget below one entry: one entry
+    (256, 0, 8, 9, 0): (2049280, 2049280, 6046976),
+    (256, 1, 4, 1, 7): (1263360, 1267712, 1263104),
+    (257, 300, 36, 8, 11): (1267712, 2005760, 1267200),                 # 11 bytes: one 8-byte entry of the ranks, none of the 12-byte ones
+    (257, 0, 256, 1023, 1048576): (2060288, 2060288, 10654464),
+    (1537, 0, 20, 7, 18444): (4440064, 4440064, 4439552),
+    (600, 300, 8, 4, 4611686018427387904): (6430976, 12571136, 2110976),          # a budget above N^2 entries: every pair
+    (100, 5, 8, 16, 1280001): (999168, 1024256, 2204416),
+    (75000, 0, 256, 10, 0): (588086016, 588086016, 597718784),
+    (75000, 25000, 256, 17, 67108864): (252541952, 314143232, 271807232),
+    (300000, 1, 16, 3, -1): (739837696, 739840768, 739837184),
+}
+
+
+def test_workspace_sizes_are_those_before_the_shared_driver(lib):
+    """The workspace layouts are part of the C ABI's contract with callers that size their own buffers: the move of the list protocol into
+    csrc/dic_candlist.h changes none of them.  Host arithmetic, no device: N = 1, a full block, one row past it, the default budget (0 and negative), budgets
+    below one entry and above every pair."""
+    for (n, m, d, t, b), want in WORKSPACES_BEFORE_CANDLIST.items():
+        got = (lib.dic_knn_workspace(n, d, b), lib.dic_knn_neighbors_workspace(n, m, d, b), lib.dic_knn_ranks_workspace(n, d, t, b))
+        assert got == want, (n, m, d, t, b)
+
+
 def test_python_argument_errors():
     X = np.zeros((10, 8), np.float32)
     with pytest.raises(ValueError, match='n_neighbors <= n_samples_fit'):

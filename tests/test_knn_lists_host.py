@@ -374,7 +374,7 @@ def test_neighbour_list_kernels_do_not_spill_to_scratch():
     names = re.findall(r'Function Name: (\S+)', res.stderr)
     scratch = [int(v) for v in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', res.stderr)]
     spills = [int(v) for v in re.findall(r'VGPRs Spill: (\d+)', res.stderr)]
-    for kernel in ('knl_exact_kernel', 'knl_window_kernel', 'knl_mask_cols_kernel', 'kn_count_kernel', 'kn_gather_kernel'):
+    for kernel in ('knl_exact_kernel', 'kn_window_kernel', 'pt_mask_cols_kernel', 'kn_count_kernel', 'kn_gather_kernel'):
         assert any(kernel in n for n in names), kernel
     assert len(scratch) == len(names) == len(spills)
     assert max(scratch) == 0 and max(spills) == 0, list(zip(names, scratch, spills))

@@ -410,7 +410,7 @@ def test_meanshift_kernels_do_not_spill_to_scratch():
     names = re.findall(r'Function Name: (\S+)', res.stderr)
     scratch = [int(v) for v in re.findall(r'ScratchSize \[bytes/lane\]: (\d+)', res.stderr)]
     spills = [int(v) for v in re.findall(r'VGPRs Spill: (\d+)', res.stderr)]
-    for kernel in ('ms_seed_prep_kernel', 'ms_mask_cols_kernel', 'ms_members_kernel', 'ms_recheck_kernel', 'ms_shift_kernelILi1ELi1E', 'ms_shift_kernelILi4ELi1E',
+    for kernel in ('ms_seed_prep_kernel', 'pt_mask_cols_kernel', 'ms_members_kernel', 'ms_recheck_kernel', 'ms_shift_kernelILi1ELi1E', 'ms_shift_kernelILi4ELi1E',
                    'ms_shift_kernelILi4ELi4E', 'ms_nearest_kernel', 'pt_prep_kernel', 'pt_block_max_kernel'):
         assert any(kernel in n for n in names), kernel
     assert len(scratch) == len(names) == len(spills)
