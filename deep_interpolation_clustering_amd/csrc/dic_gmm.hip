@@ -21,7 +21,7 @@
 // sklearn the M-step of the converging iteration is kept.  A done restart is skipped by both kernels: status[6], which the pass writes and the reduction
 // reads, tells the reduction whether its pass ran -- the done flag itself is rewritten by the reduction's component-0 workgroup while the others may not have
 // started.
-#include "dic_common.h"
+#include "dic_gmm_common.h"
 
 namespace dic {
 
@@ -31,8 +31,6 @@ constexpr int GM_RPW = 4;                         // rows a wave takes at once
 constexpr int GM_TILE = GM_WAVES * GM_RPW;        // rows of a tile
 constexpr int GM_MAX_BLOCKS = kNumCU;
 constexpr int GM_SLOTS = DIC_MAX_CLUSTERS;        // components a thread of the M-phase can own
-constexpr double GM_LOG_2PI = 1.8378770664093453;
-constexpr double GM_NK_EPS = 10.0 * 2.220446049250313e-16;
 enum { GM_EM = 0, GM_ESTEP = 1, GM_LABELS = 2, GM_RESP = 3 };
 // status words (f64): 0 done, 1 iterations, 2 stopped by tol, 3 last lower bound, 4 tol, 5 max_iter, 6 (internal) the last pass ran
 
@@ -155,7 +153,7 @@ __global__ __launch_bounds__(GM_THREADS) void gm_pass_kernel(GmArgs a) {
             double s = 0.0;
             for (int d = lane; d < a.d0; d += kWave) s += log(var[(size_t)k * D + d]);
             s = wave_sum(s);
-            if (lane == 0) s_lc[k] = (log(wt[k]) - 0.5 * ((double)a.d0 * GM_LOG_2PI)) - 0.5 * s;
+            if (lane == 0) s_lc[k] = (log(wt[k]) - 0.5 * ((double)a.d0 * GMM_LOG_2PI)) - 0.5 * s;
         }
         __syncthreads();
     }
@@ -230,23 +228,7 @@ __global__ __launch_bounds__(GM_THREADS) void gm_pass_kernel(GmArgs a) {
     }
 }
 
-// sum_b p[b * stride] in block order: GM_BATCH loads in flight (a plain loop waits for one trip to memory per block, 256 in a row), the additions strictly
-// sequential -- the bits of the plain loop
-constexpr int GM_BATCH = 32;
-__device__ __forceinline__ double gm_sum_blocks(const double* p, size_t stride, int nblk) {
-#pragma clang fp contract(off)
-    double s = 0.0;
-    int b = 0;
-    for (; b + GM_BATCH <= nblk; b += GM_BATCH) {
-        double v[GM_BATCH];
-#pragma unroll
-        for (int u = 0; u < GM_BATCH; ++u) v[u] = p[(size_t)(b + u) * stride];
-#pragma unroll
-        for (int u = 0; u < GM_BATCH; ++u) s += v[u];
-    }
-    for (; b < nblk; ++b) s += p[(size_t)b * stride];
-    return s;
-}
+constexpr int GM_BATCH = 32;          // loads in flight of gmm_sum_blocks
 
 struct GmReduce {
     const double* part; int nblk;
@@ -266,15 +248,15 @@ __global__ __launch_bounds__(GM_THREADS) void gm_mstep_kernel(GmReduce a) {
     if (a.em && st[6] == 0.0) return;          // (the pass skipped this restart: it was done)
     const size_t P = gm_part_words(K, D);
     const double* part = a.part + (size_t)run * a.nblk * P;
-    if (tid < K) s_n[tid] = gm_sum_blocks(part + tid, P, a.nblk) + GM_NK_EPS;
-    if (a.em && k == 0 && tid == kWave) s_lse = gm_sum_blocks(part + K + 2 * (size_t)K * D, P, a.nblk);          // (the second wave, beside the first's n_k)
+    if (tid < K) s_n[tid] = gmm_sum_blocks<GM_BATCH>(part + tid, P, a.nblk) + GMM_NK_EPS;
+    if (a.em && k == 0 && tid == kWave) s_lse = gmm_sum_blocks<GM_BATCH>(part + K + 2 * (size_t)K * D, P, a.nblk);          // (the second wave, beside the first's n_k)
     __syncthreads();
     const double nk = s_n[k];
     double v = 0.0;
     if (tid < D) {
         const size_t o = (size_t)k * D + tid;
-        const double sx = gm_sum_blocks(part + K + o, P, a.nblk);
-        const double sxx = gm_sum_blocks(part + K + (size_t)K * D + o, P, a.nblk);
+        const double sx = gmm_sum_blocks<GM_BATCH>(part + K + o, P, a.nblk);
+        const double sxx = gmm_sum_blocks<GM_BATCH>(part + K + (size_t)K * D + o, P, a.nblk);
         const double m = sx / nk;
         const double e2 = sxx / nk;
         const double m2 = m * m;
@@ -298,33 +280,12 @@ __global__ __launch_bounds__(GM_THREADS) void gm_mstep_kernel(GmReduce a) {
         double ws = 0.0;
         for (int j = 0; j < K; ++j) ws += s_n[j] / fn;
         a.w[(size_t)run * K + k] = (nk / fn) / ws;
-        if (a.em && k == 0) {
-            const double lb = s_lse / fn;
-            const double prev = st[3];
-            const int it = (int)st[1];
-            if (it < a.lb_stride) a.lower_bounds[(size_t)run * a.lb_stride + it] = lb;
-            st[1] = (double)(it + 1);
-            st[3] = lb;
-            if (fabs(lb - prev) < st[4]) { st[0] = 1.0; st[2] = 1.0; }
-            else if ((double)(it + 1) >= st[5]) st[0] = 1.0;
-        }
+        if (a.em && k == 0) gmm_end_iteration(st, s_lse, fn, a.lower_bounds, a.lb_stride, run);
     }
 }
 
 __global__ void gm_sum_kernel(const double* part, int nblk, double* out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *out = gm_sum_blocks(part, 1, nblk);
-}
-
-static int gm_check_points(const char* what, const float* X, long ldx, int64_t N, int D, int D0, int K) {
-    DIC_REQUIRE(X, DIC_ERR_INVALID_ARG, "%s: NULL pointer", what);
-    DIC_REQUIRE(N >= 2, DIC_ERR_INVALID_ARG, "%s: N=%lld: expected at least 2 points", what, (long long)N);
-    DIC_REQUIRE(D > 0 && ldx >= D && D0 >= 1 && D0 <= D && K >= 1, DIC_ERR_INVALID_ARG, "%s: N=%lld D=%d D0=%d ldx=%ld K=%d", what, (long long)N, D, D0, ldx, K);
-    DIC_REQUIRE(D <= 4 * kWave && D % 4 == 0 && ldx % 4 == 0, DIC_ERR_UNSUPPORTED, "%s: D=%d (row stride %ld): at most %d, multiples of 4", what, D, ldx,
-                4 * kWave);
-    DIC_REQUIRE(K <= DIC_MAX_CLUSTERS, DIC_ERR_UNSUPPORTED, "%s: K=%d: at most %d components", what, K, DIC_MAX_CLUSTERS);
-    DIC_REQUIRE(N < (1LL << 30), DIC_ERR_UNSUPPORTED, "%s: N=%lld: fewer than 2^30 points", what, (long long)N);
-    DIC_REQUIRE(((uintptr_t)X & 15) == 0, DIC_ERR_UNSUPPORTED, "%s: X must be 16-B aligned", what);
-    return DIC_OK;
+    if (threadIdx.x == 0 && blockIdx.x == 0) *out = gmm_sum_blocks<GM_BATCH>(part, 1, nblk);
 }
 
 template <int MODE>
@@ -354,7 +315,7 @@ size_t dic_gmm_workspace(int64_t N, int D, int K, int n_runs) {
 int dic_gmm_em_iter(const float* X, long ldx, int64_t N, int D, int D0, int K, int n_runs, int cov_type, double reg_covar, const double* shift, double* weights,
                     double* means, double* variances, double* status, double* lower_bounds, int lb_stride, void* workspace, size_t workspace_bytes,
                     dic_stream_t stream) {
-    const int rc = gm_check_points("gmm_em_iter", X, ldx, N, D, D0, K);
+    const int rc = gmm_check_points("gmm_em_iter", X, ldx, N, D, D0, K);
     if (rc) return rc;
     DIC_REQUIRE(shift && weights && means && variances && status && lower_bounds && workspace, DIC_ERR_INVALID_ARG, "gmm_em_iter: NULL pointer");
     DIC_REQUIRE(n_runs >= 1 && n_runs <= 65535 && lb_stride >= 1 && (cov_type == 0 || cov_type == 1) && reg_covar >= 0.0, DIC_ERR_INVALID_ARG,
@@ -379,7 +340,7 @@ int dic_gmm_em_iter(const float* X, long ldx, int64_t N, int D, int D0, int K, i
 int dic_gmm_estep(const float* X, long ldx, int64_t N, int D, int D0, int K, const double* shift, const double* weights, const double* means,
                   const double* variances, double* lse, double* log_resp, int32_t* labels, double* sum_lse, void* workspace, size_t workspace_bytes,
                   dic_stream_t stream) {
-    const int rc = gm_check_points("gmm_estep", X, ldx, N, D, D0, K);
+    const int rc = gmm_check_points("gmm_estep", X, ldx, N, D, D0, K);
     if (rc) return rc;
     DIC_REQUIRE(shift && weights && means && variances && workspace, DIC_ERR_INVALID_ARG, "gmm_estep: NULL pointer");
     DIC_REQUIRE(((uintptr_t)workspace & 15) == 0, DIC_ERR_UNSUPPORTED, "gmm_estep: the workspace must be 16-B aligned");
@@ -400,7 +361,7 @@ int dic_gmm_estep(const float* X, long ldx, int64_t N, int D, int D0, int K, con
 int dic_gmm_mstep_labels(const float* X, long ldx, int64_t N, int D, int D0, int K, int n_runs, int cov_type, double reg_covar, const double* shift,
                          const int32_t* labels, const double* resp, double* weights, double* means, double* variances, void* workspace,
                          size_t workspace_bytes, dic_stream_t stream) {
-    const int rc = gm_check_points("gmm_mstep_labels", X, ldx, N, D, D0, K);
+    const int rc = gmm_check_points("gmm_mstep_labels", X, ldx, N, D, D0, K);
     if (rc) return rc;
     DIC_REQUIRE(shift && weights && means && variances && workspace, DIC_ERR_INVALID_ARG, "gmm_mstep_labels: NULL pointer");
     DIC_REQUIRE((labels != nullptr) != (resp != nullptr), DIC_ERR_INVALID_ARG, "gmm_mstep_labels: exactly one of labels and resp");

@@ -18,7 +18,7 @@
 //                     other.  The inverse is solved by columns of P: thread j owns column j and reads only U and its own earlier results.
 // No floating-point atomics, no dependence on a neighbouring restart, nothing synchronises the stream.  A done restart is skipped by every kernel: status[6],
 // written by the pass alone, says whether the pass ran (the done flag itself is rewritten by gf_params_kernel and gf_factor_kernel).
-#include "dic_common.h"
+#include "dic_gmm_common.h"
 
 namespace dic {
 
@@ -28,8 +28,7 @@ constexpr int GF_THREADS = 256;
 constexpr int GF_TILE = 64;                       // rows of a tile: 4 waves x 16
 constexpr int GF_MAX_BLOCKS = kNumCU;
 constexpr int GF_MAX_DIM = 256;
-constexpr double GF_LOG_2PI = 1.8378770664093453;
-constexpr double GF_NK_EPS = 10.0 * 2.220446049250313e-16;
+static_assert(GF_MAX_DIM == 4 * kWave, "gmm_check_points admits 4 * kWave columns");
 enum { GF_W_LOGR = 0, GF_W_LABELS = 1, GF_W_RESP = 2, GF_W_ONES = 3 };          // where the scatter kernel takes its weights from
 enum { GF_C_FULL = 0, GF_C_TSUM = 1, GF_C_TIED = 2 };                           // what the covariance kernel does
 
@@ -138,7 +137,7 @@ __global__ __launch_bounds__(GF_THREADS) void gf_pass_kernel(GfArgs a) {
         s_ld[tid] = a.logdet[(size_t)run * a.kc + (a.kc == 1 ? 0 : tid)];
     }
     const size_t mat = (size_t)D * D;
-    const double d0_log2pi = (double)a.d0 * GF_LOG_2PI;
+    const double d0_log2pi = (double)a.d0 * GMM_LOG_2PI;
     double* part = a.part + ((size_t)run * gridDim.x + blockIdx.x) * gf_part_words(K, D);
     double pn = 0.0, pl = 0.0;
     double stage[NB];
@@ -363,22 +362,7 @@ __global__ __launch_bounds__(GF_THREADS) void gf_scatter_kernel(GfScatter a) {
     }
 }
 
-// sum_b p[b * stride] in block order: GF_BATCH loads in flight, the additions strictly sequential
-constexpr int GF_BATCH = 16;
-__device__ __forceinline__ double gf_sum_blocks(const double* p, size_t stride, int nblk) {
-#pragma clang fp contract(off)
-    double s = 0.0;
-    int b = 0;
-    for (; b + GF_BATCH <= nblk; b += GF_BATCH) {
-        double v[GF_BATCH];
-#pragma unroll
-        for (int u = 0; u < GF_BATCH; ++u) v[u] = p[(size_t)(b + u) * stride];
-#pragma unroll
-        for (int u = 0; u < GF_BATCH; ++u) s += v[u];
-    }
-    for (; b < nblk; ++b) s += p[(size_t)b * stride];
-    return s;
-}
+constexpr int GF_BATCH = 16;          // loads in flight of gmm_sum_blocks
 
 struct GfParams {
     const double* part; int nblk;
@@ -396,27 +380,18 @@ __global__ __launch_bounds__(GF_THREADS) void gf_params_kernel(GfParams a) {
     if (a.em && st[6] == 0.0) return;
     const size_t P = gf_part_words(K, D);
     const double* part = a.part + (size_t)run * a.nblk * P;
-    if (tid < K) s_n[tid] = gf_sum_blocks(part + tid, P, a.nblk) + GF_NK_EPS;
-    if (a.em && k == 0 && tid == kWave) s_lse = gf_sum_blocks(part + K + (size_t)K * D, P, a.nblk);
+    if (tid < K) s_n[tid] = gmm_sum_blocks<GF_BATCH>(part + tid, P, a.nblk) + GMM_NK_EPS;
+    if (a.em && k == 0 && tid == kWave) s_lse = gmm_sum_blocks<GF_BATCH>(part + K + (size_t)K * D, P, a.nblk);
     __syncthreads();
     const double nk = s_n[k];
-    if (tid < D) a.mu[((size_t)run * K + k) * D + tid] = gf_sum_blocks(part + K + (size_t)k * D + tid, P, a.nblk) / nk;
+    if (tid < D) a.mu[((size_t)run * K + k) * D + tid] = gmm_sum_blocks<GF_BATCH>(part + K + (size_t)k * D + tid, P, a.nblk) / nk;
     if (tid == 0) {
         const double fn = (double)a.n;
         double ws = 0.0;
         for (int j = 0; j < K; ++j) ws += s_n[j] / fn;
         a.w[(size_t)run * K + k] = (nk / fn) / ws;
         a.nk[(size_t)run * K + k] = nk;
-        if (a.em && k == 0) {
-            const double lb = s_lse / fn;
-            const double prev = st[3];
-            const int it = (int)st[1];
-            if (it < a.lb_stride) a.lower_bounds[(size_t)run * a.lb_stride + it] = lb;
-            st[1] = (double)(it + 1);
-            st[3] = lb;
-            if (fabs(lb - prev) < st[4]) { st[0] = 1.0; st[2] = 1.0; }
-            else if ((double)(it + 1) >= st[5]) st[0] = 1.0;
-        }
+        if (a.em && k == 0) gmm_end_iteration(st, s_lse, fn, a.lower_bounds, a.lb_stride, run);
     }
 }
 
@@ -438,11 +413,11 @@ __global__ __launch_bounds__(GF_THREADS) void gf_cov_kernel(GfCov a) {
     const size_t mat = (size_t)D * D, e = (size_t)i * D + j;
     double c;
     if (a.mode == GF_C_TSUM) {
-        c = gf_sum_blocks(a.slab + e, mat, a.slabs);
+        c = gmm_sum_blocks<GF_BATCH>(a.slab + e, mat, a.slabs);
     } else if (i >= a.d0) {          // the padding: the identity
         c = i == j ? 1.0 : 0.0;
     } else if (a.mode == GF_C_FULL) {
-        const double s = gf_sum_blocks(a.slab + ((size_t)run * K + kk) * a.slabs * mat + e, mat, a.slabs);
+        const double s = gmm_sum_blocks<GF_BATCH>(a.slab + ((size_t)run * K + kk) * a.slabs * mat + e, mat, a.slabs);
         const double* mu = a.mu + ((size_t)run * K + kk) * D;
         const double t = s / a.nk[(size_t)run * K + kk];
         const double m2 = mu[i] * mu[j];
@@ -592,20 +567,14 @@ __global__ __launch_bounds__(GF_THREADS) void gf_factor_kernel(GfFactor a) {
 }
 
 __global__ void gf_sum_kernel(const double* part, size_t stride, int nblk, double* out) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) *out = gf_sum_blocks(part, stride, nblk);
+    if (threadIdx.x == 0 && blockIdx.x == 0) *out = gmm_sum_blocks<GF_BATCH>(part, stride, nblk);
 }
 
 static int gf_check_points(const char* what, const float* X, long ldx, int64_t N, int D, int D0, int K, int cov_type) {
-    DIC_REQUIRE(X, DIC_ERR_INVALID_ARG, "%s: NULL pointer", what);
-    DIC_REQUIRE(N >= 2, DIC_ERR_INVALID_ARG, "%s: N=%lld: expected at least 2 points", what, (long long)N);
-    DIC_REQUIRE(D > 0 && ldx >= D && D0 >= 1 && D0 <= D && K >= 1, DIC_ERR_INVALID_ARG, "%s: N=%lld D=%d D0=%d ldx=%ld K=%d", what, (long long)N, D, D0, ldx, K);
-    DIC_REQUIRE(cov_type == 2 || cov_type == 3, DIC_ERR_INVALID_ARG, "%s: cov_type=%d: 2 (full) or 3 (tied)", what, cov_type);
-    DIC_REQUIRE(D <= GF_MAX_DIM && D % 4 == 0 && ldx % 4 == 0, DIC_ERR_UNSUPPORTED, "%s: D=%d (row stride %ld): at most %d, multiples of 4", what, D, ldx,
-                GF_MAX_DIM);
-    DIC_REQUIRE(K <= DIC_MAX_CLUSTERS, DIC_ERR_UNSUPPORTED, "%s: K=%d: at most %d components", what, K, DIC_MAX_CLUSTERS);
-    DIC_REQUIRE(N < (1LL << 30), DIC_ERR_UNSUPPORTED, "%s: N=%lld: fewer than 2^30 points", what, (long long)N);
-    DIC_REQUIRE(((uintptr_t)X & 15) == 0, DIC_ERR_UNSUPPORTED, "%s: X must be 16-B aligned", what);
-    return DIC_OK;
+    const int rc = gmm_check_points(what, X, ldx, N, D, D0, K);
+    if (rc == DIC_ERR_INVALID_ARG) return rc;
+    DIC_REQUIRE(cov_type == 2 || cov_type == 3, DIC_ERR_INVALID_ARG, "%s: cov_type=%d: 2 (full) or 3 (tied)", what, cov_type);          // (before the unsupported shapes)
+    return rc;
 }
 
 static size_t gf_pass_lds(int NB, int K) { return ((size_t)2 * 256 * NB + (size_t)GF_TILE * K + GF_TILE + 2 * (size_t)K) * sizeof(double); }

@@ -2,51 +2,31 @@
 diagonal and spherical ones: the p2 / p4 ``--cluster_method gmm --gmm_covariance_type full | tied`` branches.
 
 The latents are 256 strongly correlated outputs of an auto-encoder; a diagonal mixture spends components on describing correlation, a full one does not.  The
-model, the control flow (scikit-learn 1.7.2's, the restarts advancing together, one host read of the done flags every ``_POLL_EVERY`` iterations) and the
-shifted points are ``gmm.py``'s; the arithmetic is the f64 definition in include/dic_hip.h: the E-step (x - mu_k) P_k and the weighted scatter matrices run on
-the f64 matrix cores, the Cholesky factors P_k = L_k^-T are computed on the device, and every sum has a fixed order, so two fits give the same bits.
+model, the estimator surface, the control flow and the shifted points are ``_gmm_base.py``'s, shared with ``gmm.py``; this file adds the native calls, the
+Cholesky factors of its covariances and the total scatter matrix of the tied type.  The arithmetic is the f64 definition in include/dic_hip.h: the E-step
+(x - mu_k) P_k and the weighted scatter matrices run on the f64 matrix cores, the Cholesky factors P_k = L_k^-T are computed on the device, and every sum has
+a fixed order, so two fits give the same bits.
 
 Outputs are NumPy f64, like sklearn's.  The module imports neither sklearn nor scipy; there is no CPU fallback.
 """
 from __future__ import annotations
 
-import numbers
-import warnings
-
 import numpy as np
 import torch
 
 from . import _native as N
-from .gmm import _NOT_CONVERGED, _POLL_EVERY, GaussianMixture, _dev64, _Points
-from .kmeans import KMeans, _pp_init
+from ._gmm_base import _dev64, _MixtureBase, _Points, estep_outputs, new_status, run_em, workspace
 
 COV_TYPES = {'full': 2, 'tied': 3}
 _ILL_DEFINED = ('Fitting the mixture model failed because some components have ill-defined empirical covariance (for instance caused by singleton or collapsed '
                 'samples). Try to decrease the number of components, increase reg_covar, or scale the input data.')
-
-
-def _require_bytes(nbytes, device, n, d, k, runs, cov_type):
-    free = torch.cuda.mem_get_info(device)[0]
-    if nbytes > free:
-        raise MemoryError('the %s-covariance Gaussian mixture of %d points needs %d bytes on the device, %d are free: log r (8 N K), the partial sums and the '
-                          'slab matrices of the scatter kernel (8 K D^2 each for full covariances; K = %d, D = %d), per restart (%d)'
-                          % ('full' if cov_type == 2 else 'tied', n, nbytes, free, k, d, runs))
+_NEEDS = ('-covariance Gaussian mixture of {n} points needs {nbytes} bytes on the device, {free} are free: log r (8 N K), the partial sums and the '
+          'slab matrices of the scatter kernel (8 K D^2 each for full covariances; K = {k}, D = {d}), per restart ({runs})')
 
 
 def _workspace(pts, K, n_runs, cov_type):
-    nbytes = int(N.lib().dic_gmm_full_workspace(pts.n, pts.d, K, n_runs, cov_type))
-    if nbytes == 0:
-        raise ValueError('gmm_full: N=%d D=%d K=%d n_init=%d is outside the kernel\'s limits (2 <= N < 2^30, K <= %d)' % (pts.n, pts.d, K, n_runs, N.MAX_CLUSTERS))
-    _require_bytes(nbytes, pts.x.device, pts.n, pts.d, K, n_runs, cov_type)
-    return torch.empty(max(16, nbytes), dtype=torch.uint8, device=pts.x.device)
-
-
-def new_status(n_runs, tol, max_iter, device):
-    status = torch.zeros((n_runs, 8), dtype=torch.float64, device=device)
-    status[:, 3] = -float('inf')
-    status[:, 4] = float(tol)
-    status[:, 5] = float(max_iter)
-    return status
+    return workspace(pts, K, n_runs, lambda *shape: N.lib().dic_gmm_full_workspace(*shape, cov_type), 'gmm_full',
+                     'the ' + ('full' if cov_type == 2 else 'tied') + _NEEDS)
 
 
 def factor(cov, d0):
@@ -89,34 +69,20 @@ def em(pts, cov_type, reg_covar, par, status, max_iter, ws=None):
     (n_runs, max_iter) numpy, NaN beyond a restart's iterations)."""
     L = N.lib()
     n_runs, K = par['w'].shape
-    dev = pts.x.device
-    lbs = torch.full((n_runs, max_iter), float('nan'), dtype=torch.float64, device=dev)
     ws = _workspace(pts, K, n_runs, cov_type) if ws is None else ws
     st = N.stream_of(pts.x)
-    it = 0
-    while it < max_iter:
-        for _ in range(min(_POLL_EVERY, max_iter - it)):
-            N.check(L.dic_gmm_full_em_iter(N.ptr(pts.x), pts.x.stride(0), pts.n, pts.d, pts.d0, K, n_runs, cov_type, float(reg_covar), N.ptr(pts.shift),
-                                           N.ptr(par['w']), N.ptr(par['mu']), N.ptr(par['cov']), N.ptr(par['P']), N.ptr(par['log_det']), N.ptr(par.get('total')),
-                                           N.ptr(status), N.ptr(lbs), max_iter, N.ptr(ws), ws.numel(), st), 'dic_gmm_full_em_iter')
-            it += 1
-        if bool((status[:, 0] != 0).all()):          # the only host sync of the loop
-            break
-    return status.cpu().numpy(), lbs.cpu().numpy()
+
+    def iterate(lbs):
+        N.check(L.dic_gmm_full_em_iter(N.ptr(pts.x), pts.x.stride(0), pts.n, pts.d, pts.d0, K, n_runs, cov_type, float(reg_covar), N.ptr(pts.shift),
+                                       N.ptr(par['w']), N.ptr(par['mu']), N.ptr(par['cov']), N.ptr(par['P']), N.ptr(par['log_det']), N.ptr(par.get('total')),
+                                       N.ptr(status), N.ptr(lbs), max_iter, N.ptr(ws), ws.numel(), st), 'dic_gmm_full_em_iter')
+    return run_em(iterate, status, max_iter)
 
 
 def estep(pts, cov_type, w, mu, P, log_det, lse=False, log_resp=False, labels=False, total=False, ws=None):
     """The E-step of one parameter set ((K), (K, D), (Kc, D, D), (Kc) f64 on the device): a dict of the requested outputs, as ``gmm.estep``."""
-    K, dev = w.shape[-1], pts.x.device
-    out = {}
-    if lse:
-        out['lse'] = torch.empty(pts.n, dtype=torch.float64, device=dev)
-    if log_resp:
-        out['log_resp'] = torch.empty((pts.n, K), dtype=torch.float64, device=dev)
-    if labels:
-        out['labels'] = torch.empty(pts.n, dtype=torch.int32, device=dev)
-    if total:
-        out['total'] = torch.empty(1, dtype=torch.float64, device=dev)
+    K = w.shape[-1]
+    out = estep_outputs(pts, K, lse, log_resp, labels, total)
     ws = _workspace(pts, K, 1, cov_type) if ws is None else ws
     N.check(N.lib().dic_gmm_full_estep(N.ptr(pts.x), pts.x.stride(0), pts.n, pts.d, pts.d0, K, cov_type, N.ptr(pts.shift), N.ptr(w.contiguous()),
                                        N.ptr(mu.contiguous()), N.ptr(P.contiguous()), N.ptr(log_det.contiguous()), N.ptr(out.get('lse')),
@@ -148,95 +114,31 @@ def _pad_square(a, D, device):
     return torch.as_tensor(out, device=device)
 
 
-class FullGaussianMixture:
+class FullGaussianMixture(_MixtureBase):
+    _NAME = 'gmm_full'
+    _count_parameters = staticmethod(n_parameters)
+
     def __init__(self, n_components=1, *, covariance_type='full', tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1, init_params='kmeans', weights_init=None,
                  means_init=None, precisions_init=None, random_state=None):
         if covariance_type not in COV_TYPES:
             raise ValueError("covariance_type must be 'full' or 'tied' (gmm.GaussianMixture has 'diag' and 'spherical'), got %r" % (covariance_type,))
-        if isinstance(n_components, bool) or not isinstance(n_components, (numbers.Integral, np.integer)) or n_components < 1:
-            raise ValueError('n_components must be an int >= 1, got %r' % (n_components,))
-        if n_components > N.MAX_CLUSTERS:
-            raise ValueError('n_components=%d > %d: outside the compiled limit' % (n_components, N.MAX_CLUSTERS))
-        if isinstance(n_init, bool) or not isinstance(n_init, (numbers.Integral, np.integer)) or n_init < 1:
-            raise ValueError('n_init must be an int >= 1, got %r' % (n_init,))
-        if isinstance(max_iter, bool) or not isinstance(max_iter, (numbers.Integral, np.integer)) or max_iter < 1:
-            raise ValueError('max_iter must be an int >= 1, got %r' % (max_iter,))
-        if not tol >= 0 or not reg_covar >= 0:
-            raise ValueError('tol and reg_covar must be >= 0, got %r and %r' % (tol, reg_covar))
-        if init_params not in ('kmeans', 'k-means++', 'random', 'random_from_data'):
-            raise ValueError("init_params must be 'kmeans', 'k-means++', 'random' or 'random_from_data', got %r" % (init_params,))
-        self.n_components = int(n_components)
-        self.covariance_type = covariance_type
-        self.tol = float(tol)
-        self.reg_covar = float(reg_covar)
-        self.max_iter = int(max_iter)
-        self.n_init = int(n_init)
-        self.init_params = init_params
-        self.weights_init = weights_init
-        self.means_init = means_init
-        self.precisions_init = precisions_init
-        self.random_state = random_state
+        super().__init__(n_components, covariance_type, tol, reg_covar, max_iter, n_init, init_params, weights_init, means_init, precisions_init, random_state)
 
-    _random_state = KMeans._random_state
+    @property
+    def _per_component(self):          # (tied covariances are shared and stay)
+        return ('covariances_', 'precisions_', 'precisions_cholesky_', '_log_det') if self.covariance_type == 'full' else ()
 
-    def _check_inits(self, d0):
-        """The given initial parameters, checked: w, mu, and the precisions as (P, log_det) per matrix, factorised once on the host."""
-        K = self.n_components
-        out = {}
-        if self.weights_init is not None:
-            w = np.asarray(self.weights_init, dtype=np.float64)
-            if w.shape != (K,):
-                raise ValueError("The parameter 'weights' should have the shape of (%d,), but got %s" % (K, w.shape))
-            if (w < 0).any() or (w > 1).any() or not np.allclose(np.abs(1.0 - w.sum()), 0.0):
-                raise ValueError("The parameter 'weights' should be in the range [0, 1] and normalized")
-            out['w'] = w
-        if self.means_init is not None:
-            m = np.asarray(self.means_init, dtype=np.float64)
-            if m.shape != (K, d0):
-                raise ValueError("The parameter 'means' should have the shape of (%d, %d), but got %s" % (K, d0, m.shape))
-            out['mu'] = m
-        if self.precisions_init is not None:
-            p = np.asarray(self.precisions_init, dtype=np.float64)
-            want = (K, d0, d0) if self.covariance_type == 'full' else (d0, d0)
-            if p.shape != want:
-                raise ValueError("The parameter '%s precision' should have the shape of %s, but got %s" % (self.covariance_type, want, p.shape))
-            mats = p.reshape(-1, d0, d0)
-            facs = []
-            for m in mats:
-                if not (np.allclose(m, m.T) and np.all(np.linalg.eigvalsh(m) > 0.0)):
-                    raise ValueError("'%s precision' should be symmetric, positive-definite" % self.covariance_type)
-                facs.append(_host_factor(m))
-            out['prec'] = (np.stack([f[0] for f in facs]), np.array([f[1] for f in facs]))
-        return out
-
-    def _draw(self, pts, init_labels):
-        """(labels, resp) of the n_init restarts: every random number is drawn here, restart by restart, in sklearn's order (``gmm.py``'s draws)."""
-        K, n_runs, dev = self.n_components, self.n_init, pts.x.device
-        rs = self._random_state()
-        if init_labels is not None:
-            return torch.as_tensor(np.ascontiguousarray(init_labels, dtype=np.int32).reshape(n_runs, pts.n), device=dev), None
-        if self.init_params == 'random':
-            resp = np.empty((n_runs, pts.n, K), dtype=np.float64)
-            for r in range(n_runs):
-                u = rs.uniform(size=(pts.n, K))
-                resp[r] = u / u.sum(axis=1)[:, np.newaxis]
-            return None, torch.as_tensor(resp, device=dev)
-        labels = torch.full((n_runs, pts.n), -1, dtype=torch.int32, device=dev)
-        comps = torch.arange(K, dtype=torch.int32, device=dev)
-        for r in range(n_runs):
-            if self.init_params == 'kmeans':
-                km = KMeans(n_clusters=K, n_init=1, random_state=rs).fit(pts.x[:, :pts.d0])
-                labels[r] = torch.as_tensor(km.labels_.astype(np.int32), device=dev)
-            elif self.init_params == 'random_from_data':
-                idx = rs.choice(pts.n, size=K, replace=False)
-                labels[r, torch.as_tensor(idx, device=dev)] = comps
-            else:          # 'k-means++'
-                rows = _pp_init(pts.x.contiguous(), K, 1, rs)[0]
-                for k in range(K):
-                    if torch.isnan(rows[k]).any():
-                        raise ValueError('gmm_full: the points contain NaN')
-                    labels[r, int(torch.nonzero((pts.x == rows[k]).all(dim=1))[0])] = k
-        return labels, None
+    def _check_precisions(self, p, d0):
+        """The given precisions as (P, log_det) per matrix, factorised once on the host."""
+        want = (self.n_components, d0, d0) if self.covariance_type == 'full' else (d0, d0)
+        if p.shape != want:
+            raise ValueError("The parameter '%s precision' should have the shape of %s, but got %s" % (self.covariance_type, want, p.shape))
+        facs = []
+        for m in p.reshape(-1, d0, d0):
+            if not (np.allclose(m, m.T) and np.all(np.linalg.eigvalsh(m) > 0.0)):
+                raise ValueError("'%s precision' should be symmetric, positive-definite" % self.covariance_type)
+            facs.append(_host_factor(m))
+        return np.stack([f[0] for f in facs]), np.array([f[1] for f in facs])
 
     def _initial_parameters(self, pts, ws, status, init_labels=None, total=None):
         K, n_runs, dev, D = self.n_components, self.n_init, pts.x.device, pts.d
@@ -268,13 +170,6 @@ class FullGaussianMixture:
             status[:, 7] = 0.0
         return par
 
-    def _points(self, X):
-        if not hasattr(self, 'weights_'):
-            raise RuntimeError('This FullGaussianMixture instance is not fitted yet.')
-        if hasattr(X, 'shape') and len(X.shape) == 2 and X.shape[1] != self.n_features_in_:
-            raise ValueError('X has %d features, but FullGaussianMixture is expecting %d features as input.' % (X.shape[1], self.n_features_in_))
-        return _Points(X, shift=self._shift)
-
     def _device_parameters(self, pts):
         """The fitted parameters against the training shift, padded; the factor of the kept covariances is the kept one (``precisions_cholesky_``)."""
         K, dev, d0 = self.n_components, pts.x.device, self.n_features_in_
@@ -284,7 +179,9 @@ class FullGaussianMixture:
         ld = _dev64(self._log_det, (-1,), dev)
         return _dev64(self.weights_, (K,), dev), mu, P, ld
 
-    # -- estimator API ------------------------------------------------------------------------
+    def _estep_points(self, pts, **want):
+        return estep(pts, COV_TYPES[self.covariance_type], *self._device_parameters(pts), **want)
+
     def _fit_points(self, pts, init_labels=None, total=None):
         K, d0 = self.n_components, pts.d0
         if pts.n < K:
@@ -298,21 +195,7 @@ class FullGaussianMixture:
         self._scatter_total = par.get('total')
         if (status[:, 7] != 0).any():
             raise ValueError(_ILL_DEFINED)
-        best, max_lb = 0, -np.inf
-        for r in range(self.n_init):          # _base.py:283-290: the first of equal bounds wins
-            if status[r, 3] > max_lb or max_lb == -np.inf:
-                best, max_lb = r, status[r, 3]
-        self.converged_ = bool(status[best, 2] != 0)
-        if not self.converged_:
-            warnings.warn(_NOT_CONVERGED, UserWarning)
-        self.n_iter_ = int(status[best, 1])
-        self.lower_bound_ = float(status[best, 3])
-        self.lower_bounds_ = lbs[best, :self.n_iter_].copy()
-        self.n_features_in_ = d0
-        self._shift = pts.shift_host.copy()
-        self._means_shifted = par['mu'][best, :, :d0].cpu().numpy()
-        self.weights_ = par['w'][best].cpu().numpy()
-        self.means_ = self._means_shifted + self._shift[None, :]
+        best = self._publish(pts, status, lbs, par['w'], par['mu'])
         C = par['cov'][best, :, :d0, :d0].cpu().numpy()
         P = par['P'][best, :, :d0, :d0].cpu().numpy()
         self._log_det = par['log_det'][best].cpu().numpy()
@@ -325,63 +208,6 @@ class FullGaussianMixture:
         # the final E-step (_base.py:321-325): labels consistent with the kept parameters
         self.labels_ = estep(pts, cov, par['w'][best], par['mu'][best], par['P'][best], par['log_det'][best], labels=True, ws=ws)['labels'].cpu().numpy()
         return self
-
-    def fit(self, X, y=None):
-        return self._fit_points(_Points(X))
-
-    def fit_predict(self, X, y=None):
-        return self.fit(X).labels_
-
-    def _estep(self, X, **want):
-        pts = self._points(X)
-        return pts, estep(pts, COV_TYPES[self.covariance_type], *self._device_parameters(pts), **want)
-
-    def predict(self, X):
-        """(N,) int32 numpy: the component of largest weighted log-probability (the first of equal ones)."""
-        return self._estep(X, labels=True)[1]['labels'].cpu().numpy()
-
-    def predict_proba(self, X):
-        """(N, K) f64 numpy: the responsibilities, exp(log r)."""
-        return torch.exp(self._estep(X, log_resp=True)[1]['log_resp']).cpu().numpy()
-
-    def score_samples(self, X):
-        """(N,) f64 numpy: the log-likelihood of every row."""
-        return self._estep(X, lse=True)[1]['lse'].cpu().numpy()
-
-    def score(self, X, y=None):
-        """The mean log-likelihood per row, summed in fixed order on the device."""
-        pts, out = self._estep(X, total=True)
-        return float(out['total'].cpu().numpy()[0]) / pts.n
-
-    def reorder(self, order):
-        """Renumber the components: new component j is old component ``order[j]``.  Tied covariances are shared and stay."""
-        order = np.asarray(order, dtype=np.int64)
-        if sorted(order.tolist()) != list(range(self.n_components)):
-            raise ValueError('order must be a permutation of 0..%d, got %r' % (self.n_components - 1, order.tolist()))
-        names = ['weights_', 'means_', '_means_shifted']
-        if self.covariance_type == 'full':
-            names += ['covariances_', 'precisions_', 'precisions_cholesky_', '_log_det']
-        for name in names:
-            setattr(self, name, getattr(self, name)[order].copy())
-        if hasattr(self, 'labels_'):
-            inverse = np.empty_like(order)
-            inverse[order] = np.arange(len(order))
-            self.labels_ = inverse[self.labels_].astype(self.labels_.dtype)
-        return self
-
-    def _n_parameters(self):
-        return n_parameters(self.n_components, self.n_features_in_, self.covariance_type)
-
-    bic = GaussianMixture.bic
-    aic = GaussianMixture.aic
-
-    def sample(self, n_samples=1):
-        raise NotImplementedError('sample is not implemented: the accelerated path fits and scores; draw from means_ / covariances_ with NumPy')
-
-    def get_params(self, deep=True):
-        return dict(n_components=self.n_components, covariance_type=self.covariance_type, tol=self.tol, reg_covar=self.reg_covar, max_iter=self.max_iter,
-                    n_init=self.n_init, init_params=self.init_params, weights_init=self.weights_init, means_init=self.means_init,
-                    precisions_init=self.precisions_init, random_state=self.random_state)
 
 
 def gmm_full_sweep(X, ks, **kw):
