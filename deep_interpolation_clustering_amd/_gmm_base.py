@@ -1,5 +1,5 @@
-"""What the two Gaussian mixture front ends share: ``gmm.py`` (diagonal and spherical covariances) and ``gmm_full.py`` (full and tied ones) add their native
-calls, their covariance parameters and their errors to the estimator below.
+"""What the Gaussian mixture front ends share: ``gmm.py`` (diagonal and spherical covariances), ``gmm_full.py`` (full and tied ones) and ``bgmm.py`` (the
+variational Bayesian mixture) add their native calls, their parameters and their errors to the estimator below.
 
 Control flow follows scikit-learn 1.7.2 (``mixture/_base.py`` fit_predict :223-330, ``_initialize_parameters`` :98-141; ``_gaussian_mixture.py``
 ``_initialize`` :788-817, bic / aic :881-933).  The points enter shifted by their column means ``c`` (x' = (double)x - c, the means are kept as mu - c on the
@@ -203,7 +203,8 @@ class _MixtureBase:
         self.n_features_in_ = pts.d0
         self._shift = pts.shift_host.copy()
         self._means_shifted = mu[best, :, :pts.d0].cpu().numpy()
-        self.weights_ = w[best].cpu().numpy()
+        if w is not None:          # (the Bayesian mixture forms its weights from the Dirichlet parameters)
+            self.weights_ = w[best].cpu().numpy()
         self.means_ = self._means_shifted + self._shift[None, :]
         return best
 

@@ -194,6 +194,13 @@ SIGNATURES = {
     'dic_gmm_em_iter': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _i, _p, _sz, _p]),
     'dic_gmm_estep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'dic_gmm_mstep_labels': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_bgmm_workspace': (_sz, [C.c_int64, _i, _i, _i]),
+    'dic_bgmm_init': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+                           _sz, _p]),
+    'dic_bgmm_em_iter': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, _i, C.c_double, C.c_double, C.c_double, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p,
+                              _i, _p, _sz, _p]),
+    'dic_bgmm_estep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    'dic_bgmm_special_probe': (_i, [_p, C.c_int64, _p, _p]),
     'dic_gmm_full_workspace': (_sz, [C.c_int64, _i, _i, _i, _i]),
     'dic_gmm_full_em_iter': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _sz, _p]),
     'dic_gmm_full_estep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),

@@ -1,7 +1,8 @@
 // What the two Gaussian mixture files share (dic_gmm.hip: diagonal and spherical covariances; dic_gmm_full.hip: full and tied ones): the constants of the
 // definition in include/dic_hip.h, the block-order sum both reductions are made of, the end of an EM iteration -- the lower bound's bookkeeping and THE STOPPING
 // RULE, which defines converged_ and n_iter_ of both estimators -- and the checks of the points every entry point starts with.  The passes, the M-steps and
-// the factor stay in their files: the two families share no arithmetic beyond these.
+// the factor stay in their files: the two families share no arithmetic beyond these.  dic_bgmm.hip (the variational Bayesian mixture) takes the block-order
+// sum, the bookkeeping of an iteration's end -- with its own lower bound, a sum -- and the checks of the points from here.
 #pragma once
 #include "dic_common.h"
 

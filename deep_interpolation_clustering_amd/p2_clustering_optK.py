@@ -45,6 +45,13 @@ lower bound, BIC and AIC of the fit itself -- a likelihood-based criterion for K
 validation cohort and the --internal_metrics of the hard labels go to <metric>_gmm_aligned/plot/gmm_k.csv, the 0-based labels to plot/gmm_labels.csv, one
 column k<K> per K.
 
+``--cluster_method bgmm`` (no upstream counterpart): variational Bayesian Gaussian mixtures (bgmm.py) of k_max components, one fit per value of
+--bgmm_concentration (default 1 / k_max) with --n_init restarts, --gmm_covariance_type diag | spherical and --bgmm_prior_type dirichlet_process |
+dirichlet_distribution: the prior empties the components the latents do not support, so ONE fit answers how many there are.  Per concentration the active
+components, the lower bound, the iterations, the validation score and the --internal_metrics of the hard labels go to <metric>_bgmm_aligned/plot/bgmm_k.csv,
+the per-component weights to plot/bgmm_weights.csv and the labels -- the active components renumbered 0..A-1 -- to plot/bgmm_labels.csv, one column per
+concentration.
+
 ``--cluster_method snn`` (no upstream counterpart): shared-nearest-neighbour clustering of the training latents on the GPU (snn.py: the k-neighbour lists of
 knn.py, one pass over them for the similarities, no N x N matrix) -- closeness counted in shared neighbours, an integer without a scale, where the euclidean
 eps of the dbscan branch flips from all noise to one cluster within a narrow band.  ONE graph with k = --snn_k (default feat_dim + 1) serves every
@@ -126,6 +133,7 @@ from ._cluster_cli import AGREEMENT_COLUMNS, DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS,
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
 from .density_peaks import density_peaks_sweep
+from .bgmm import bgmm_sweep
 from .gmm import gmm_sweep
 from .gmm_full import gmm_full_sweep
 from .hdbscan import hdbscan_sizes
@@ -162,7 +170,11 @@ def get_arguments(argv=None):
     p.add_argument('--hdbscan_min_cluster_size', type=int, nargs='+', default=None,
                    help='(extra) min_cluster_size values of --cluster_method hdbscan; default feat_dim + 1')
     p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical', 'full', 'tied'],
-                   help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py')
+                   help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py (bgmm: diag or spherical)')
+    p.add_argument('--bgmm_concentration', type=float, nargs='+', default=None,
+                   help='(extra) weight concentration priors of --cluster_method bgmm, one fit each (default: 1 / k_max)')
+    p.add_argument('--bgmm_prior_type', default='dirichlet_process', choices=['dirichlet_process', 'dirichlet_distribution'],
+                   help='(extra) the weight prior of --cluster_method bgmm')
     p.add_argument('--snn_k', type=int, default=None, help='(extra) neighbours per point of --cluster_method snn; default feat_dim + 1')
     p.add_argument('--snn_eps', type=int, nargs='+', default=None,
                    help='(extra) shared-neighbour thresholds of --cluster_method snn, integers in [1, k]; default round(k t / 10) for t = 2..8 -- a starting '
@@ -822,6 +834,59 @@ class Gmm(_Branch):
         return df
 
 
+class Bgmm(_Branch):
+    """Bayesian Gaussian mixtures of the training latents (``bgmm.bgmm_sweep``) with ``k_max`` components, one fit per weight concentration prior of
+    ``concentrations`` (default 1 / k_max), ``n_init`` restarts each.  Per concentration: the components that are some training row's label (active), the
+    lower bound, the iterations and whether the winning restart converged, the mean log-likelihood of the validation cohort under the training model, and
+    the ``internal_metrics`` of the hard labels as ``Gmm`` computes them.  Writes plot/bgmm_k.csv (concentration, n_components, n_active, lower_bound,
+    n_iter, converged, valid_score, the metrics), plot/bgmm_weights.csv (concentration, component, weight, n_k, mean_precision, degrees_of_freedom,
+    active: one row per component and fit) and plot/bgmm_labels.csv (columns c0, c1, .. in the table's order: the active components renumbered 0..A-1 in
+    ascending component order) and returns the first table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned
+    then.  ``fits_`` keeps the fitted models [``bgmm.BayesianGaussianMixture``] of the last run that computed them, in the table's order."""
+    FILES = ('bgmm_k.csv', 'bgmm_weights.csv', 'bgmm_labels.csv')
+    COLUMNS = ['concentration', 'n_components', 'n_active', 'lower_bound', 'n_iter', 'converged', 'valid_score']
+    WEIGHT_COLUMNS = ['concentration', 'component', 'weight', 'n_k', 'mean_precision', 'degrees_of_freedom', 'active']
+
+    def __init__(self, k_max, out_path, internal_metrics, n_init=1, covariance_type='diag', concentrations=None, prior_type='dirichlet_process',
+                 metric_sample=0):
+        self.k_max, self.n_init, self.covariance_type, self.prior_type = k_max, n_init, covariance_type, prior_type
+        self.concentrations = [1.0 / k_max] if concentrations is None else [float(c) for c in concentrations]
+        self._open(out_path, internal_metrics, metric_sample)
+        self.fits_ = None
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fits_ = None
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        k_csv, weights_csv, labels_csv = self._paths()
+        Xd, Vd = device_latents(train_data), device_latents(valid_data)
+        by_c = bgmm_sweep(Xd, sorted(set(self.concentrations)), n_components=self.k_max, covariance_type=self.covariance_type, n_init=self.n_init,
+                          weight_concentration_prior_type=self.prior_type)
+        fits = [by_c[c] for c in self.concentrations]
+        rows, weight_rows, columns = [], [], {}
+        for i, (c, fit) in enumerate(zip(self.concentrations, fits)):
+            logger.info('Running concentration: {:.6g}'.format(c))
+            active = fit.active_components_
+            labels = np.searchsorted(active, fit.labels_).astype(np.int64)          # (active components -> 0..A-1, ascending)
+            valid = float(fit.score(Vd))
+            vals = self._metric_values(Xd, labels, nan_below_two=True)
+            logger.info('concentration: {:.6g}, active: {} of {}, lower_bound: {:.4f}, n_iter: {}, valid: {:.4f} '.format(
+                c, len(active), self.k_max, fit.lower_bound_, fit.n_iter_, valid) + self._metric_log(vals))
+            rows.append([c, self.k_max, len(active), fit.lower_bound_, fit.n_iter_, int(fit.converged_), valid] + vals)
+            nk = fit.degrees_of_freedom_ - fit.degrees_of_freedom_prior_          # (nu_k = nu0 + n_k)
+            for k in range(self.k_max):
+                weight_rows.append([c, k, fit.weights_[k], nk[k], fit.mean_precision_[k], fit.degrees_of_freedom_[k], int(k in active)])
+            columns['c{}'.format(i)] = labels
+        df = pd.DataFrame(rows, columns=self.COLUMNS + self.internal_metrics_names)
+        df.to_csv(k_csv, index=False, float_format='%.17g')
+        pd.DataFrame(weight_rows, columns=self.WEIGHT_COLUMNS).to_csv(weights_csv, index=False, float_format='%.17g')
+        pd.DataFrame(columns).to_csv(labels_csv, index=False)
+        logger.info('Saved for {}!.'.format(k_csv))
+        self.fits_ = fits
+        return df
+
+
 class Meanshift(_Branch):
     """Mean shift of the training latents (``meanshift.mean_shift_sweep``), one fit per bandwidth: the given ``bandwidths``, or ``estimate_bandwidth`` of the
     training latents at every quantile of ``quantiles``.  Per bandwidth: the clusters found, the orphans (``cluster_all`` off), the largest and the smallest
@@ -1131,6 +1196,8 @@ BRANCHES = {
     'kmedoids': lambda a, d, out, tr, va: Kmedoids(a.k_max, out, a.internal_metrics, a.metric_sample).train(tr, va),
     'densitypeaks': lambda a, d, out, tr, va: Densitypeaks(a.dp_k if a.dp_k is not None else a.k_max, out, a.internal_metrics, a.dp_density, a.dp_percent,
                                                            a.dp_dc, bool(a.dp_halo), a.metric_sample).train(tr, va),
+    'bgmm': lambda a, d, out, tr, va: Bgmm(a.k_max, out, a.internal_metrics, a.n_init, a.gmm_covariance_type, a.bgmm_concentration, a.bgmm_prior_type,
+                                           a.metric_sample).train(tr, va),
 }
 
 

@@ -33,6 +33,10 @@ nearest training centre; writes <cohort>_<k>.npy.
 ``gmm`` (no upstream counterpart; the kmeans branch with a mixture in place of the centres): a Gaussian mixture of --num_clusters components (--gmm_covariance_type, default
 diag) fitted to the training latents on the GPU (gmm.py; gmm_full.py for full and tied), the components re-numbered by sbp -- weights, means and covariances permuted with the map -- and every cohort
 labelled by ``predict`` of that one model; writes <cohort>_<k>.npy with ``cluster_id`` and ``cluster_prob``, the (N, K) f32 responsibilities.
+``bgmm`` (no upstream counterpart; the gmm branch with a variational Bayesian mixture, bgmm.py): one fit of the training latents with --num_clusters as the
+UPPER bound on the components (--bgmm_concentration, --bgmm_prior_type, --gmm_covariance_type diag | spherical); the active components -- those that are
+some training encounter's label -- re-numbered by sbp, every cohort labelled by ``predict`` (a row whose best component is inactive in training gets the
+best active one); writes <cohort>_bgmm-K<K>.npy with ``cluster_id`` and ``cluster_prob``, one f32 column per active component.
 ``meanshift`` (no upstream counterpart; the kmeans branch with the modes of the latent density in place of the centres, their number found by the fit): one
 mean shift fit of the training latents on the GPU (meanshift.py) at --meanshift_bandwidth, or at estimate_bandwidth(training latents,
 --meanshift_quantile); the centres re-numbered by sbp and every cohort labelled by ``predict``, the nearest centre -- with --meanshift_cluster_all 0 an
@@ -76,6 +80,7 @@ from ._cluster_cli import (AGREEMENT_COLUMNS, DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS
                            contamination_arg, dbcv_summary, noise_summary, spell)
 from .dbscan import DBSCAN
 from .density_peaks import DensityPeaks
+from .bgmm import BayesianGaussianMixture
 from .gmm import GaussianMixture
 from .gmm_full import FullGaussianMixture
 from .hdbscan import HDBSCAN
@@ -98,7 +103,11 @@ def get_arguments(argv=None):
     p.add_argument('--cluster_method', default='kmeans', choices=METHODS)
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical', 'full', 'tied'],
-                   help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py')
+                   help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py (bgmm: diag or spherical)')
+    p.add_argument('--bgmm_concentration', type=float, default=None,
+                   help='(extra) weight concentration prior of --cluster_method bgmm (default: 1 / num_clusters)')
+    p.add_argument('--bgmm_prior_type', default='dirichlet_process', choices=['dirichlet_process', 'dirichlet_distribution'],
+                   help='(extra) the weight prior of --cluster_method bgmm')
     p.add_argument('--restore_metric', default=['ae_mse', 'loss', 'delta'])
     p.add_argument('--opt_eps', type=float, default=1.9)
     p.add_argument('--hdbscan_min_cluster_size', type=int, default=None, help='(extra) min_cluster_size of --cluster_method hdbscan; default feat_dim + 1')
@@ -389,6 +398,30 @@ class Cluster(object):
         self._write_cohorts(cohorts, overwrite, '{{}}_{}.npy'.format(k), lambda cohort, data: data.update(
             cluster_id=model.predict(data['hidden']), cluster_prob=model.predict_proba(data['hidden']).astype(np.float32)))
 
+    def _bgmm(self, cohorts, overwrite):
+        """The gmm branch with a variational Bayesian mixture of --num_clusters components: one fit of the training cohort, whose prior empties the
+        components the latents do not support.  The ACTIVE components -- the labels of at least one training encounter -- are ordered by sbp as the gmm
+        branch orders its components; every cohort is labelled by ``predict`` of that model, and a row whose best component is inactive in training
+        gets the best active one.  ``cluster_prob`` holds the model's responsibilities of the active components, one column each, in the new order."""
+        k = self.args.num_clusters
+        cov = self.args.gmm_covariance_type
+        logger.info('==> Generate the Bayesian Gaussian mixture results with at most {} components'.format(k))
+        model = BayesianGaussianMixture(n_components=k, n_init=10, covariance_type=cov, weight_concentration_prior_type=self.args.bgmm_prior_type,
+                                        weight_concentration_prior=self.args.bgmm_concentration).fit(self.train_data['hidden'])
+        active = model.active_components_
+        raw = np.searchsorted(active, model.labels_).astype(np.int64)
+        align_map, _, _ = self.generate_align_map(raw, self.train_data['ob'], self.train_data['padding_mask'])
+        columns = np.empty(len(active), dtype=np.int64)
+        for old, new in align_map.items():
+            columns[new] = active[old]
+        logger.info('Active components: {} of {} ({}); a row whose best component is inactive in training gets the best active one.'.format(
+            len(active), k, columns.tolist()))
+
+        def fill(cohort, data):
+            prob = model.predict_proba(data['hidden'])[:, columns]
+            data.update(cluster_id=np.argmax(prob, axis=1).astype(np.int64), cluster_prob=prob.astype(np.float32))
+        self._write_cohorts(cohorts, overwrite, '{{}}_bgmm-K{}.npy'.format(k), fill)
+
     def _meanshift(self, cohorts, overwrite):
         """The kmeans branch with mean shift in place of k-means: one fit of the training cohort at the given or the estimated bandwidth finds the centres and
         their number, generate_align_map orders them by sbp and the centres are permuted with the map.  Every cohort, training included, is labelled by
@@ -538,7 +571,7 @@ class Cluster(object):
 
     # --cluster_method -> its branch, called with (cohorts, overwrite).  A method of METHODS without an entry ('optics') raises in pred.
     BRANCHES = {'kmeans': _kmeans, 'dl': _dl, 'dbscan': _dbscan, 'consensus': _consensus, 'hdbscan': _hdbscan, 'snn': _snn, 'spectral': _spectral,
-                'ward': _ward, 'gmm': _gmm, 'meanshift': _meanshift, 'kmedoids': _kmedoids, 'densitypeaks': _densitypeaks}
+                'ward': _ward, 'gmm': _gmm, 'meanshift': _meanshift, 'kmedoids': _kmedoids, 'densitypeaks': _densitypeaks, 'bgmm': _bgmm}
 
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)

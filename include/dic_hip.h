@@ -823,6 +823,36 @@ int dic_gmm_mstep_labels(const float* X, long ldx, int64_t N, int D, int D0, int
                          const int32_t* labels, const double* resp, double* weights, double* means, double* variances, void* workspace,
                          size_t workspace_bytes, dic_stream_t stream);
 
+/* Variational Bayesian Gaussian mixtures with diagonal (cov_type 0) or spherical (cov_type 1) covariances, every operation in f64 (csrc/dic_bgmm.hip, bgmm.py;
+ * sklearn.mixture.BayesianGaussianMixture's model, stated at the head of csrc/dic_bgmm.hip).  X, ldx, N, D, D0, K, n_runs, shift and the workspace rules as for
+ * dic_gmm_*: x' = (double)x - shift, `means` (n_runs, K, D) holds the shifted m_k, `variances` (n_runs, K, D) the normalised v_kd (spherical: one value
+ * repeated over d < D0); in the padding m = 0 and v = 1.  prior_type 0 is the Dirichlet process (stick breaking), 1 the Dirichlet distribution.  Priors:
+ * gamma0 > 0 (weight concentration), kappa0 > 0 (mean precision), nu0 > D0 - 1 (degrees of freedom), mean_prior (D) f64 DEVICE, shifted (m0 - shift, 0 in the
+ * padding), cov_prior (D) f64 DEVICE (spherical: one value repeated).  comp (n_runs, DIC_BGMM_COMP_WORDS, K) f64 DEVICE holds per component, row by row:
+ * 0 n_k, 1 kappa_k, 2 nu_k, 3 l_k = -(sum_{d < D0} log v_kd) / 2 - (D0 log nu_k) / 2, 4 log_lambda_k, 5 sum_{j < D0} lgamma((nu_k - j) / 2), 6 a_k (process)
+ * or alpha_k (distribution), 7 b_k (process; 0 otherwise), 8 E[log pi_k], 9 lc_k, the constant of log p_ik = lc_k - M_ik / 2.
+ * Sums over rows are per-workgroup f64 partials (dic_bgmm_workspace bytes), added in block order; every other sum is sequential in index order: no
+ * floating-point atomics, two calls give the same bits, and a restart's bits do not depend on the restarts beside it.  Nothing synchronises `stream`.
+ *   dic_bgmm_init: the M-step from hard labels (n_runs, N) int32 (a label outside 0 .. K - 1 gives a row of zeros) or from responsibilities (n_runs, N, K)
+ *       f64 -- exactly one of the two -- and the first constants: writes means, variances and every row of comp.
+ *   dic_bgmm_em_iter: one E+M pass, the reduction and the finish step for every restart whose done flag is clear.  status and lower_bounds as
+ *       dic_gmm_em_iter, but the lower bound is the variational bound, a sum over the rows and not a mean.
+ *   dic_bgmm_estep: the E-step of ONE parameter set: log_const (K) is row 9 of its comp.  Outputs as dic_gmm_estep, each optional.
+ *   dic_bgmm_special_probe: digamma_out[i] = psi(x[i]) by the kernels' own device function (NaN for x <= 0) and lgamma_out[i] = lgamma(x[i]) by the device
+ *       library, for n values on the DEVICE, on the null stream; either output may be NULL.  For the tests. */
+#define DIC_BGMM_COMP_WORDS 10
+size_t dic_bgmm_workspace(int64_t N, int D, int K, int n_runs);
+int dic_bgmm_init(const float* X, long ldx, int64_t N, int D, int D0, int K, int n_runs, int cov_type, int prior_type, double reg_covar, double gamma0,
+                  double kappa0, double nu0, const double* shift, const double* mean_prior, const double* cov_prior, const int32_t* labels, const double* resp,
+                  double* means, double* variances, double* comp, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_bgmm_em_iter(const float* X, long ldx, int64_t N, int D, int D0, int K, int n_runs, int cov_type, int prior_type, double reg_covar, double gamma0,
+                     double kappa0, double nu0, const double* shift, const double* mean_prior, const double* cov_prior, double* means, double* variances,
+                     double* comp, double* status, double* lower_bounds, int lb_stride, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_bgmm_estep(const float* X, long ldx, int64_t N, int D, int D0, int K, const double* shift, const double* log_const, const double* means,
+                   const double* variances, double* lse, double* log_resp, int32_t* labels, double* sum_lse, void* workspace, size_t workspace_bytes,
+                   dic_stream_t stream);
+int dic_bgmm_special_probe(const double* x, int64_t n, double* digamma_out, double* lgamma_out);
+
 /* Gaussian mixtures with full (cov_type 2) or tied (cov_type 3) covariances by EM, every operation in f64, the products on the f64 matrix cores
  * (csrc/dic_gmm_full.hip, gmm_full.py; sklearn.mixture.GaussianMixture's model).  X, D, D0, ldx, N, K, n_runs, shift, weights (n_runs, K) and means
  * (n_runs, K, D) as for dic_gmm_*: x' = (double)x - shift, `means` holds mu' = mu - shift, the columns D0 .. D - 1 are zero padding.  Kc = K for full and 1 for
