@@ -9,7 +9,7 @@ from .internal_eval import CHIndex, DBIndex, DunnIndex, Sihouette
 from .utils import logger
 
 # every --cluster_method either program accepts: p2 has no 'dl' branch, p4 no 'optics' branch (both raise once the data are loaded)
-METHODS = ('kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'snn', 'spectral', 'meanshift', 'kmedoids', 'densitypeaks', 'bgmm')
+METHODS = ('kmeans', 'dbscan', 'dl', 'optics', 'consensus', 'hdbscan', 'ward', 'gmm', 'fcm', 'snn', 'spectral', 'meanshift', 'kmedoids', 'densitypeaks', 'bgmm')
 
 INDICES = {'Dunn_Index': DunnIndex, 'Sihouette': Sihouette, 'Davies-Bouldin_Index': DBIndex, 'Calinski-Harabasz': CHIndex}
 

@@ -201,6 +201,9 @@ SIGNATURES = {
                               _i, _p, _sz, _p]),
     'dic_bgmm_estep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'dic_bgmm_special_probe': (_i, [_p, C.c_int64, _p, _p]),
+    'dic_fcm_workspace': (_sz, [C.c_int64, _i, _i, _i]),
+    'dic_fcm_iter': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, C.c_double, _p, _p, _p, _p, _i, _p, _sz, _p]),
+    'dic_fcm_memberships': (_i, [_p, C.c_long, C.c_int64, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),
     'dic_gmm_full_workspace': (_sz, [C.c_int64, _i, _i, _i, _i]),
     'dic_gmm_full_em_iter': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _i, C.c_double, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _sz, _p]),
     'dic_gmm_full_estep': (_i, [_p, C.c_long, C.c_int64, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _sz, _p]),

@@ -2,7 +2,8 @@
 // definition in include/dic_hip.h, the block-order sum both reductions are made of, the end of an EM iteration -- the lower bound's bookkeeping and THE STOPPING
 // RULE, which defines converged_ and n_iter_ of both estimators -- and the checks of the points every entry point starts with.  The passes, the M-steps and
 // the factor stay in their files: the two families share no arithmetic beyond these.  dic_bgmm.hip (the variational Bayesian mixture) takes the block-order
-// sum, the bookkeeping of an iteration's end -- with its own lower bound, a sum -- and the checks of the points from here.
+// sum, the bookkeeping of an iteration's end -- with its own lower bound, a sum -- and the checks of the points from here.  dic_fcm.hip (fuzzy c-means, no
+// mixture, but the same pass / block-order reduction / status block) takes the block-order sum and the checks, and has its own end of an iteration below.
 #pragma once
 #include "dic_common.h"
 
@@ -41,6 +42,20 @@ __device__ __forceinline__ void gmm_end_iteration(double* st, double sum_lse, do
     st[1] = (double)(it + 1);
     st[3] = lb;
     if (fabs(lb - prev) < st[4]) { st[0] = 1.0; st[2] = 1.0; }
+    else if ((double)(it + 1) >= st[5]) st[0] = 1.0;
+}
+
+// The end of a fuzzy c-means iteration of restart `run` (dic_fcm.hip), by the one thread that owns it: the same status block, word 3 the last objective J.
+// Appends J, counts the iteration and decides whether the restart is done: after iteration t >= 2 if |J_(t-1) - J_t| <= tol J_(t-1) -- a RELATIVE decrease,
+// where the mixtures compare an absolute one, and never after the first iteration, whose J belongs to the initial centres -- or when t reaches max_iter.
+__device__ __forceinline__ void fcm_end_iteration(double* st, double J, double* objectives, int obj_stride, int run) {
+#pragma clang fp contract(off)
+    const double prev = st[3];
+    const int it = (int)st[1];
+    if (it < obj_stride) objectives[(size_t)run * obj_stride + it] = J;
+    st[1] = (double)(it + 1);
+    st[3] = J;
+    if (it >= 1 && fabs(prev - J) <= st[4] * prev) { st[0] = 1.0; st[2] = 1.0; }
     else if ((double)(it + 1) >= st[5]) st[0] = 1.0;
 }
 

@@ -45,6 +45,14 @@ lower bound, BIC and AIC of the fit itself -- a likelihood-based criterion for K
 validation cohort and the --internal_metrics of the hard labels go to <metric>_gmm_aligned/plot/gmm_k.csv, the 0-based labels to plot/gmm_labels.csv, one
 column k<K> per K.
 
+``--cluster_method fcm`` (no upstream counterpart): fuzzy c-means (fcm.py: Bezdek's soft partition, memberships from distance ratios alone, the post-hoc
+counterpart of DEC's q) of the training latents on the GPU for K = 2..k_max with --n_init restarts each, one sweep per fuzzifier of --fcm_m (default 2; closer
+to 1 is harder).  Per (m, K) the objective J, the partition coefficient, its modified form, the partition entropy, Xie-Beni and the fuzzy silhouette -- criteria
+for K that need no likelihood --, the iterations, the number of coincident centre pairs (a collapsed fit: in high dimensions FCM runs all centres together,
+and the remedy is a smaller m), the partition coefficient of the validation cohort under the training centres and the --internal_metrics of the hard labels go
+to <metric>_fcm_aligned/plot/fcm_k.csv, the 0-based labels to plot/fcm_labels.csv, one column m<m>_k<K> per fit, and the centres to plot/fcm_centers.csv (m, k,
+cluster, the coordinates), %.17g.
+
 ``--cluster_method bgmm`` (no upstream counterpart): variational Bayesian Gaussian mixtures (bgmm.py) of k_max components, one fit per value of
 --bgmm_concentration (default 1 / k_max) with --n_init restarts, --gmm_covariance_type diag | spherical and --bgmm_prior_type dirichlet_process |
 dirichlet_distribution: the prior empties the components the latents do not support, so ONE fit answers how many there are.  Per concentration the active
@@ -122,6 +130,7 @@ import argparse
 import os
 import queue
 import threading
+import warnings
 import os.path as osp
 
 import numpy as np
@@ -133,6 +142,7 @@ from ._cluster_cli import AGREEMENT_COLUMNS, DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS,
 from .consensus import BINS, ConsensusKMeans
 from .dbscan import dbscan_sweep
 from .density_peaks import density_peaks_sweep
+from .fcm import fcm_sweep
 from .bgmm import bgmm_sweep
 from .gmm import gmm_sweep
 from .gmm_full import gmm_full_sweep
@@ -171,6 +181,9 @@ def get_arguments(argv=None):
                    help='(extra) min_cluster_size values of --cluster_method hdbscan; default feat_dim + 1')
     p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical', 'full', 'tied'],
                    help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py (bgmm: diag or spherical)')
+    p.add_argument('--fcm_m', type=float, nargs='+', default=[2.0],
+                   help='(extra) fuzzifiers of --cluster_method fcm, each > 1, one sweep over K per value; default 2 -- where plot/fcm_k.csv reports '
+                        'coincident centres (a collapsed fit, usual in high dimensions) choose a smaller one, e.g. 1.2')
     p.add_argument('--bgmm_concentration', type=float, nargs='+', default=None,
                    help='(extra) weight concentration priors of --cluster_method bgmm, one fit each (default: 1 / k_max)')
     p.add_argument('--bgmm_prior_type', default='dirichlet_process', choices=['dirichlet_process', 'dirichlet_distribution'],
@@ -834,6 +847,69 @@ class Gmm(_Branch):
         return df
 
 
+class Fcm(_Branch):
+    """Fuzzy c-means of the training latents (``fcm.fcm_sweep``), one sweep per fuzzifier of ``ms`` over K = 2..``k_max``, ``n_init`` restarts each.  Per
+    (m, K): the objective, the partition coefficient, its modified form, the partition entropy, Xie-Beni and the fuzzy silhouette of the training latents, the
+    iterations and whether the winning restart converged, the number of coincident centre pairs (non-zero: the fit collapsed), the partition coefficient
+    of the validation cohort under the training centres, and the ``internal_metrics`` of the hard labels as ``Gmm`` computes them.  Writes plot/fcm_k.csv
+    (``COLUMNS``, the metrics), plot/fcm_labels.csv (columns m<m>_k<K>, 0-based) and plot/fcm_centers.csv (m, k, cluster, x0, x1, ..), %.17g, and returns
+    the first table.  Existing files are left alone unless ``overwrite`` is set; the table on disk is returned then.  ``fits_`` keeps the fitted models
+    {(m, K): ``fcm.FuzzyCMeans``} of the last run that computed them."""
+    FILES = ('fcm_k.csv', 'fcm_labels.csv', 'fcm_centers.csv')
+    COLUMNS = ['m', 'k', 'objective', 'partition_coefficient', 'modified_partition_coefficient', 'partition_entropy', 'xie_beni', 'fuzzy_silhouette',
+               'n_iter', 'converged', 'n_coincident', 'valid_partition_coefficient']
+
+    def __init__(self, k_max, out_path, internal_metrics, n_init=1, ms=(2.0,), metric_sample=0):
+        self.ks = list(range(2, k_max + 1))
+        self.n_init, self.ms = n_init, [float(m) for m in ms]
+        self._open(out_path, internal_metrics, metric_sample)
+        self.fits_ = None
+
+    @staticmethod
+    def column(m, k):
+        return 'm{:g}_k{}'.format(m, k)
+
+    def train(self, train_data, valid_data, **kwargs):
+        overwrite = kwargs.get('overwrite', False)
+        self.fits_ = None
+        if self._left_alone(overwrite):
+            return self._table_on_disk()
+        k_csv, labels_csv, centers_csv = self._paths()
+        Xd, Vd = device_latents(train_data), device_latents(valid_data)
+        fits, rows, columns, centers = {}, [], {}, []
+        for m in self.ms:
+            logger.info('Running m: {:g}'.format(m))
+            with warnings.catch_warnings(record=True) as caught:          # (a collapsed fit is a row of the table here, and one log line)
+                warnings.simplefilter('always')
+                by_k = fcm_sweep(Xd, self.ks, m=m, n_init=self.n_init)
+            for w in caught:
+                logger.info(str(w.message))
+            for k in self.ks:
+                logger.info('Running K: {}'.format(k))
+                fit = fits[(m, k)] = by_k[k]
+                labels = np.unique(fit.labels_, return_inverse=True)[1].astype(np.int64)          # (a centre without a row of its own is skipped by the indices)
+                fs = float(fit.fuzzy_silhouette(Xd))
+                u = fit.memberships(Vd)
+                valid_pc = float((u * u).sum() / len(u))
+                vals = self._metric_values(Xd, labels, nan_below_two=True)
+                logger.info('m: {:g}, k: {}, objective: {:.4f}, PC: {:.4f}, PE: {:.4f}, XB: {:.4f}, FS: {:.4f}, n_iter: {}, coincident: {}, valid PC: {:.4f} '.format(
+                    m, k, fit.objective_, fit.partition_coefficient_, fit.partition_entropy_, fit.xie_beni_, fs, fit.n_iter_, len(fit.coincident_centers_),
+                    valid_pc) + self._metric_log(vals))
+                rows.append([m, k, fit.objective_, fit.partition_coefficient_, fit.modified_partition_coefficient_, fit.partition_entropy_, fit.xie_beni_, fs,
+                             fit.n_iter_, int(fit.converged_), len(fit.coincident_centers_), valid_pc] + vals)
+                columns[self.column(m, k)] = fit.labels_
+                centers.append(np.column_stack([np.full(k, m), np.full(k, k), np.arange(k), fit.cluster_centers_]))
+        df = pd.DataFrame(rows, columns=self.COLUMNS + self.internal_metrics_names)
+        df.to_csv(k_csv, index=False, float_format='%.17g')
+        pd.DataFrame(columns).to_csv(labels_csv, index=False)
+        width = centers[0].shape[1] - 3
+        pd.DataFrame(np.concatenate(centers), columns=['m', 'k', 'cluster'] + ['x{}'.format(c) for c in range(width)]).astype(
+            {'k': np.int64, 'cluster': np.int64}).to_csv(centers_csv, index=False, float_format='%.17g')
+        logger.info('Saved for {}!.'.format(k_csv))
+        self.fits_ = fits
+        return df
+
+
 class Bgmm(_Branch):
     """Bayesian Gaussian mixtures of the training latents (``bgmm.bgmm_sweep``) with ``k_max`` components, one fit per weight concentration prior of
     ``concentrations`` (default 1 / k_max), ``n_init`` restarts each.  Per concentration: the components that are some training row's label (active), the
@@ -1189,6 +1265,7 @@ BRANCHES = {
     'hdbscan': lambda a, d, out, tr, va: Hdbscan(min_samples=d + 1, min_cluster_sizes=a.hdbscan_min_cluster_size or [d + 1], out_path=out).train(tr, va),
     'ward': lambda a, d, out, tr, va: Ward(a.k_max, out, a.internal_metrics, a.metric_sample).train(tr, va),
     'gmm': lambda a, d, out, tr, va: Gmm(a.k_max, out, a.internal_metrics, a.n_init, a.gmm_covariance_type, a.metric_sample).train(tr, va),
+    'fcm': lambda a, d, out, tr, va: Fcm(a.k_max, out, a.internal_metrics, a.n_init, a.fcm_m, a.metric_sample).train(tr, va),
     'snn': _snn_branch,
     'spectral': lambda a, d, out, tr, va: Spectral(a.k_max, out, a.internal_metrics, a.spectral_k, a.spectral_assign, a.metric_sample).train(tr, va),
     'meanshift': lambda a, d, out, tr, va: Meanshift(out, a.internal_metrics, a.meanshift_quantile, a.meanshift_bandwidth, a.meanshift_bin_seeding,

@@ -33,6 +33,9 @@ nearest training centre; writes <cohort>_<k>.npy.
 ``gmm`` (no upstream counterpart; the kmeans branch with a mixture in place of the centres): a Gaussian mixture of --num_clusters components (--gmm_covariance_type, default
 diag) fitted to the training latents on the GPU (gmm.py; gmm_full.py for full and tied), the components re-numbered by sbp -- weights, means and covariances permuted with the map -- and every cohort
 labelled by ``predict`` of that one model; writes <cohort>_<k>.npy with ``cluster_id`` and ``cluster_prob``, the (N, K) f32 responsibilities.
+``fcm`` (no upstream counterpart; the kmeans branch with fuzzy c-means in place of k-means, fcm.py): one fit of the training latents with --num_clusters
+centres and the fuzzifier --fcm_m (default 2; a fit whose centres coincide warns: choose a smaller one), the centres re-numbered by sbp and every cohort
+labelled by ``predict`` of that one model; writes <cohort>_<k>.npy with ``cluster_id``, ``cluster_prob``, the (N, K) f32 memberships, and ``fcm_m``.
 ``bgmm`` (no upstream counterpart; the gmm branch with a variational Bayesian mixture, bgmm.py): one fit of the training latents with --num_clusters as the
 UPPER bound on the components (--bgmm_concentration, --bgmm_prior_type, --gmm_covariance_type diag | spherical); the active components -- those that are
 some training encounter's label -- re-numbered by sbp, every cohort labelled by ``predict`` (a row whose best component is inactive in training gets the
@@ -80,6 +83,7 @@ from ._cluster_cli import (AGREEMENT_COLUMNS, DBCV_CLUSTER_COLUMNS, DBCV_COLUMNS
                            contamination_arg, dbcv_summary, noise_summary, spell)
 from .dbscan import DBSCAN
 from .density_peaks import DensityPeaks
+from .fcm import FuzzyCMeans
 from .bgmm import BayesianGaussianMixture
 from .gmm import GaussianMixture
 from .gmm_full import FullGaussianMixture
@@ -104,6 +108,8 @@ def get_arguments(argv=None):
     p.add_argument('--num_clusters', type=int, default=4, help='The number of cluster centers')
     p.add_argument('--gmm_covariance_type', default='diag', choices=['diag', 'spherical', 'full', 'tied'],
                    help='(extra) covariances of --cluster_method gmm; full and tied run gmm_full.py (bgmm: diag or spherical)')
+    p.add_argument('--fcm_m', type=float, default=2.0,
+                   help='(extra) the fuzzifier of --cluster_method fcm, > 1; default 2 -- a fit that warns of coincident centres wants a smaller one, e.g. 1.2')
     p.add_argument('--bgmm_concentration', type=float, default=None,
                    help='(extra) weight concentration prior of --cluster_method bgmm (default: 1 / num_clusters)')
     p.add_argument('--bgmm_prior_type', default='dirichlet_process', choices=['dirichlet_process', 'dirichlet_distribution'],
@@ -398,6 +404,21 @@ class Cluster(object):
         self._write_cohorts(cohorts, overwrite, '{{}}_{}.npy'.format(k), lambda cohort, data: data.update(
             cluster_id=model.predict(data['hidden']), cluster_prob=model.predict_proba(data['hidden']).astype(np.float32)))
 
+    def _fcm(self, cohorts, overwrite):
+        """The kmeans branch with fuzzy c-means in place of k-means: one fit of the training cohort, generate_align_map orders the centres by sbp as the
+        gmm branch orders its components and the model is permuted with the map.  Every cohort, training included, is labelled by ``predict`` of that
+        model; ``cluster_prob`` holds its memberships, so ``cluster_id`` is their first maximum, and ``fcm_m`` the fuzzifier they were formed with."""
+        k, m = self.args.num_clusters, float(self.args.fcm_m)
+        logger.info('==> Generate the fuzzy c-means results with opt-k: {}, m: {:g}'.format(k, m))
+        model = FuzzyCMeans(n_clusters=k, m=m, n_init=10).fit(self.train_data['hidden'])
+        raw = model.labels_.astype(np.int64)
+        if len(set(raw.tolist())) != k:
+            raise ValueError('fuzzy c-means left {} of its {} centres without a training encounter: choose a smaller --num_clusters or a smaller '
+                             '--fcm_m'.format(k - len(set(raw.tolist())), k))
+        self._reorder(model, raw)
+        self._write_cohorts(cohorts, overwrite, '{{}}_{}.npy'.format(k), lambda cohort, data: data.update(
+            cluster_id=model.predict(data['hidden']), cluster_prob=model.predict_proba(data['hidden']).astype(np.float32), fcm_m=m))
+
     def _bgmm(self, cohorts, overwrite):
         """The gmm branch with a variational Bayesian mixture of --num_clusters components: one fit of the training cohort, whose prior empties the
         components the latents do not support.  The ACTIVE components -- the labels of at least one training encounter -- are ordered by sbp as the gmm
@@ -571,7 +592,7 @@ class Cluster(object):
 
     # --cluster_method -> its branch, called with (cohorts, overwrite).  A method of METHODS without an entry ('optics') raises in pred.
     BRANCHES = {'kmeans': _kmeans, 'dl': _dl, 'dbscan': _dbscan, 'consensus': _consensus, 'hdbscan': _hdbscan, 'snn': _snn, 'spectral': _spectral,
-                'ward': _ward, 'gmm': _gmm, 'meanshift': _meanshift, 'kmedoids': _kmedoids, 'densitypeaks': _densitypeaks, 'bgmm': _bgmm}
+                'ward': _ward, 'gmm': _gmm, 'fcm': _fcm, 'meanshift': _meanshift, 'kmedoids': _kmedoids, 'densitypeaks': _densitypeaks, 'bgmm': _bgmm}
 
     def pred(self, **kwargs):
         overwrite = kwargs.get('overwrite', False)

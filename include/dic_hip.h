@@ -853,6 +853,29 @@ int dic_bgmm_estep(const float* X, long ldx, int64_t N, int D, int D0, int K, co
                    dic_stream_t stream);
 int dic_bgmm_special_probe(const double* x, int64_t n, double* digamma_out, double* lgamma_out);
 
+/* Fuzzy c-means (Bezdek) with the fuzzifier m, every operation in f64 (csrc/dic_fcm.hip, fcm.py).  X, ldx, N, D, K, n_runs, shift and the workspace rules as
+ * for dic_gmm_* (there is no D0: the padding columns are zero in the points and in the centres and add nothing); m must be finite and > 1.  centers
+ * (n_runs, K, D) f64 DEVICE holds v' = v - shift; every x enters as x' = (double)x - shift.  With p = 1 / (m - 1):
+ *   d2_ik = sum_d (x'_id - v'_kd)^2;  dmin_i = min_k d2_ik;
+ *   dmin_i > 0:  r_ik = dmin_i / d2_ik,  t_ik = r_ik if m == 2 exactly, else exp(p log r_ik),  u_ik = t_ik / sum_k t_ik;
+ *   dmin_i == 0: u_ik = [d2_ik == 0] / #{k : d2_ik == 0};
+ *   w_ik = u_ik^2 if m == 2, else exp(m log u_ik), 0 where u_ik == 0;  v'_k = sum_i w_ik x'_i / sum_i w_ik (a component without weight keeps its centre);
+ *   J = sum_ik w_ik d2_ik,  S2 = sum_ik u_ik^2,  SE = sum_ik u_ik log u_ik (0 log 0 = 0), all from the centres that ENTERED the pass.
+ * Sums over rows are per-workgroup f64 partials (dic_fcm_workspace bytes: K + K D + 3 doubles per workgroup and restart), added in block order: no
+ * floating-point atomics, two calls give the same bits, and a restart's bits do not depend on the restarts beside it.  Nothing synchronises `stream`.
+ *   dic_fcm_workspace: bytes of the workspace (16-B aligned) of the other calls, 0 for arguments outside the limits.
+ *   dic_fcm_iter: one iteration of every restart whose done flag is clear; centers are updated in place, done restarts keep theirs.  status (n_runs,
+ *       DIC_GMM_STATUS_WORDS) f64 IN/OUT, the words as for dic_gmm_em_iter with [3] the last J.  The pass writes J_t to objectives[run * obj_stride +
+ *       iterations] (dropped beyond obj_stride) and sets done after iteration t >= 2 if |J_(t-1) - J_t| <= tol J_(t-1) ([2] = 1), or when iterations
+ *       reaches max_iter; the first iteration never stops, and the update of the stopping iteration is kept.
+ *   dic_fcm_memberships: ONE centre set.  Outputs, each optional (NULL): u (N, K) f64, labels (N) int32 (the first maximum of u), d2 (N, K) f64,
+ *       sums (3) f64 = J, S2, SE in block order. */
+size_t dic_fcm_workspace(int64_t N, int D, int K, int n_runs);
+int dic_fcm_iter(const float* X, long ldx, int64_t N, int D, int K, int n_runs, double m, const double* shift, double* centers, double* status,
+                 double* objectives, int obj_stride, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+int dic_fcm_memberships(const float* X, long ldx, int64_t N, int D, int K, double m, const double* shift, const double* centers, double* u, int32_t* labels,
+                        double* d2, double* sums, void* workspace, size_t workspace_bytes, dic_stream_t stream);
+
 /* Gaussian mixtures with full (cov_type 2) or tied (cov_type 3) covariances by EM, every operation in f64, the products on the f64 matrix cores
  * (csrc/dic_gmm_full.hip, gmm_full.py; sklearn.mixture.GaussianMixture's model).  X, D, D0, ldx, N, K, n_runs, shift, weights (n_runs, K) and means
  * (n_runs, K, D) as for dic_gmm_*: x' = (double)x - shift, `means` holds mu' = mu - shift, the columns D0 .. D - 1 are zero padding.  Kc = K for full and 1 for
