@@ -52,10 +52,11 @@ def _segment_sum(values, lab, K):
 
 class PairStats:
     """Result of one pair pass: ``labels`` (N) encoded 0..K-1, ``counts`` (K), ``S`` / ``Dmin`` (N,K) f32 and ``own_max`` (N),
-    all in the caller's row order."""
+    all in the caller's row order.  ``route``: the pass that produced it -- 'pairdist' / 'intra_sums' (the difference form on the VALU), 'rowsums' / 'totals' (the
+    matrix cores)."""
 
-    def __init__(self, labels, counts, S, Dmin, own_max, S_own=None, totals=None):
-        self.labels, self.counts, self.S, self.Dmin, self.own_max, self.S_own, self.totals = labels, counts, S, Dmin, own_max, S_own, totals
+    def __init__(self, labels, counts, S, Dmin, own_max, S_own=None, totals=None, route=None):
+        self.labels, self.counts, self.S, self.Dmin, self.own_max, self.S_own, self.totals, self.route = labels, counts, S, Dmin, own_max, S_own, totals, route
         self.K = int(counts.numel())
 
     def intra_sums(self):
@@ -86,9 +87,43 @@ def _tile_list(counts_host):
 # The sums-only all-pairs pass goes to the matrix cores from this many points on.  Its distances come from the norm form on split bf16 planes: a pair's d^2 is off
 # by ~2^-17 |x - mean| |y - mean| (random sign), which the sums over thousands of pairs average away (tests: <= 2e-6 of a row's largest sum at 70 001 x 256) but
 # which shows on a handful of close points in few dimensions (4e-6 at 63 x 4) -- and below this size the difference-form kernel takes well under a millisecond.
-ROWSUM_MIN_POINTS = 8192
-PAIRDIST_MAX_K = 64         # dic_cluster_pairdist: clusters per pass
+ROWSUM_MIN_POINTS = 8192    # (0: every sums-only call takes the pass, whatever the labelling -- the tests of the kernel itself)
 ROWSUM_WORKGROUPS = 256     # dic_cluster_pair_rowsums: one persistent workgroup per CU, each a contiguous range of the tile list
+# ... and only for labellings on which that error stays small against the distances the silhouette is made of.  The pass takes every point relative to ONE
+# centre, so a pair's d^2 is off by ~2^-17 of the points' squared distances from it (dic_pairtile.h: < 2^-12 proven), whatever the pair's own distance: inside
+# a cluster much tighter than the cloud, or between two centroids much closer than it, sqrt(max(a_ij, 0)) is noise with a positive bias.  A labelling is taken
+# as safe when  the smallest mean squared radius of a cluster of two or more points >= ROWSUM_SAFE_RATIO x F  and  the smallest squared distance of two
+# centroids >= ROWSUM_SAFE_SEPARATION x F,  F the largest mean squared distance of a cluster's points from the mean of all points  (f64, from two segment sums;
+# per cluster and not over all points: a small cluster far from a large one sits far from the mean without moving the average).  A constant is 4 x the largest
+# ratio at which the NumPy emulation of the pass
+# (oracle/pairtile_emulation.py; sweep of the cluster spread at 1 500 x 16, K = 3, three seeds, plain and shifted by 1000: scripts/validity_sweep.py ->
+# profiles/validity_parity.json) still moves the silhouette by its bar, rtol 1e-5 + atol 1e-6, or a cluster's total of own-cluster sums (the inertias) by rtol
+# 1e-5: 0.0113, set by the sums -- the radii feed both.  The distances between clusters enter the silhouette alone, which crosses at 1.2e-5 (k-means splits of
+# one blob, as every K sweep produces them, have centroids ~1e-3 F apart and stay on the pass).  Everything else goes to the difference form below (~40 ms at
+# 75 000 x 256).
+ROWSUM_SAFE_RATIO = 0.046
+ROWSUM_SAFE_SEPARATION = 4.9e-5
+
+
+def rowsum_geometry(xs, lab_sorted, counts):
+    """(smallest mean squared radius of a cluster of two or more points, smallest squared centroid distance, largest mean over a cluster of the squared distance
+    from the mean of all points), f64, of the points ``xs`` (N, D) with labels 0..K-1 -- what ``rowsum_is_safe`` compares."""
+    K = int(counts.numel())
+    xc = xs.double()
+    xc -= xc.mean(0, keepdim=True)
+    sq = torch.einsum('ij,ij->i', xc, xc)
+    cnt = counts.double()
+    cen = _segment_sum(xc, lab_sorted, K) / cnt[:, None]
+    far = _segment_sum(sq, lab_sorted, K) / cnt
+    radius = (far - (cen * cen).sum(1)).clamp(min=0.0)        # mean |x - c|^2 = mean |x|^2 - |c|^2 (centred: no cancellation of the offset)
+    radius = radius.masked_fill(counts < 2, float('inf'))
+    sep = torch.cdist(cen, cen, compute_mode='donot_use_mm_for_euclid_dist').square().masked_fill(torch.eye(K, dtype=torch.bool, device=xs.device), float('inf'))
+    return float(radius.min()), float(sep.min()), float(far.max())
+
+
+def rowsum_is_safe(xs, lab_sorted, counts):
+    radius, sep, far = rowsum_geometry(xs, lab_sorted, counts)
+    return radius >= ROWSUM_SAFE_RATIO * far and sep >= ROWSUM_SAFE_SEPARATION * far
 
 
 def _row_tile_list(counts_host, n):
@@ -146,7 +181,7 @@ def intra_totals(x, labels):
     totals = torch.empty(K, dtype=torch.float64, device=x.device)
     N.check(L.dic_cluster_intra_totals(N.ptr(xs), xs.stride(0), N.ptr(seg), N.ptr(centres), n, d, K, N.ptr(tiles) if tiles.numel() else None, tiles.shape[0],
                                        N.ptr(totals), N.ptr(ws), ws.numel(), N.stream_of(xs)), 'dic_cluster_intra_totals')
-    return PairStats(lab, counts, None, None, None, None, totals)
+    return PairStats(lab, counts, None, None, None, None, totals, route='totals')
 
 
 def pair_stats(x, labels, need_min=True, need_max=True, intra_only=False):
@@ -170,11 +205,10 @@ def pair_stats(x, labels, need_min=True, need_max=True, intra_only=False):
         N.check(N.lib().dic_cluster_intra_sums(N.ptr(xs), N.ptr(seg), n, d, K, N.ptr(S_own), N.stream_of(xs)), 'dic_cluster_intra_sums')
         out = torch.empty_like(S_own)
         out[order] = S_own
-        return PairStats(lab, counts, None, None, None, out)
+        return PairStats(lab, counts, None, None, None, out, route='intra_sums')
     S = torch.empty((n, K), device=x.device, dtype=torch.float32)
-    if not need_min and not need_max and d <= TOTALS_MAX_D and (n >= ROWSUM_MIN_POINTS or K > PAIRDIST_MAX_K):
-        # only the sums (the silhouette): the all-pairs pass on the matrix cores (dic_cluster_pair_rowsums), points relative to their mean -- also below
-        # ROWSUM_MIN_POINTS when dic_cluster_pairdist cannot take K (DBSCAN labellings, noise as a cluster of its own, often have more than 64)
+    if not need_min and not need_max and d <= TOTALS_MAX_D and n >= ROWSUM_MIN_POINTS and (ROWSUM_MIN_POINTS == 0 or rowsum_is_safe(xs, lab[order], counts)):
+        # only the sums (the silhouette): the all-pairs pass on the matrix cores (dic_cluster_pair_rowsums), points relative to their mean
         tiles, group_start, n_slots = _row_tile_list(counts.cpu().numpy(), n)
         tiles, group_start = torch.from_numpy(tiles).to(x.device), torch.from_numpy(group_start).to(x.device)
         centre = xs.mean(0, keepdim=True, dtype=torch.float64).float().contiguous()
@@ -184,7 +218,7 @@ def pair_stats(x, labels, need_min=True, need_max=True, intra_only=False):
                                            N.ptr(ws), ws.numel(), N.stream_of(xs)), 'dic_cluster_pair_rowsums')
         out = torch.empty_like(S)
         out[order] = S
-        return PairStats(lab, counts, out, None, None)
+        return PairStats(lab, counts, out, None, None, route='rowsums')
     Dmin = torch.empty_like(S) if need_min else None
     omax = torch.empty(n, device=x.device, dtype=torch.float32) if need_max else None
     N.check(N.lib().dic_cluster_pairdist(N.ptr(xs), N.ptr(seg), n, d, K, N.ptr(S), N.ptr(Dmin), N.ptr(omax), N.stream_of(xs)),
@@ -196,7 +230,7 @@ def pair_stats(x, labels, need_min=True, need_max=True, intra_only=False):
         out = torch.empty_like(t)
         out[order] = t
         return out
-    return PairStats(lab, counts, unsort(S), unsort(Dmin), unsort(omax))
+    return PairStats(lab, counts, unsort(S), unsort(Dmin), unsort(omax), route='pairdist')
 
 
 # ---------------------------------------------------------------------------- gap-statistic inertia (p2:334-351)
@@ -215,10 +249,15 @@ def inertia_v2(x, labels, stats=None):
 
 # ---------------------------------------------------------------------------- validity indices (internal_eval.py)
 def silhouette_samples(x, labels, stats=None):
+    if stats is None:                          # (the check comes before any pair pass)
+        x = _device_points(x)
+        labels, K = _encode(labels, x.device)
+    else:
+        K = stats.K
+    n_pts = labels.numel() if stats is None else stats.labels.numel()
+    if not 1 < K < n_pts:
+        raise ValueError('Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)' % K)
     st = stats or pair_stats(x, labels, need_min=False, need_max=False)
-    n_pts = st.labels.numel()
-    if not 1 < st.K < n_pts:
-        raise ValueError('Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)' % st.K)
     S = st.S.double()
     cnt = st.counts.double()
     own_mask = torch.nn.functional.one_hot(st.labels, st.K).bool()
@@ -276,7 +315,8 @@ def davies_bouldin_score(x, labels):
     x64, cnt, cen = _centroids(x, lab, K)
     dist = ((x64 - cen[lab]) ** 2).sum(1).sqrt()
     intra = _segment_sum(dist, lab, K) / cnt
-    cd = torch.cdist(cen, cen)
+    cd = torch.cdist(cen, cen, compute_mode='donot_use_mm_for_euclid_dist')          # (differences: from 26 centroids on the default takes the norm form, whose
+                                                                                     #  diagonal is rounding noise and not 0 -- and (s_a + s_a) / noise is the largest ratio)
     if bool(torch.allclose(intra, torch.zeros_like(intra))) or bool(torch.allclose(cd, torch.zeros_like(cd))):
         return 0.0
     cd = cd.masked_fill(cd == 0, float('inf'))

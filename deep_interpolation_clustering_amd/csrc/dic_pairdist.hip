@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void pairdist_kernel(const float* __restrict__
         int lab = -1;
         if (i < N) {
             lab = 0;
-            while (lab + 1 < K && seg[lab + 1] <= i) ++lab;        // K <= 64: a short scan
+            while (lab + 1 < K && seg[lab + 1] <= i) ++lab;        // a scan: K is small against the tile work that follows
         }
         own[r] = lab;
     }
@@ -159,27 +159,29 @@ __global__ __launch_bounds__(256) void pairdist_kernel(const float* __restrict__
 // Per-cluster f64 sums of the rows of an f64 matrix: out[k][c] = sum over rows i with lab[i] == k of v[i][c] -- the centroids of the Calinski-Harabasz / Davies-
 // Bouldin scores and the per-cluster distance sums of the gap statistic (internal_eval.py:112-147, p2_clustering_optK.py:334-351).  Until round 6 a one-hot f64
 // GEMM through rocBLAS (the last library GEMM of the K sweep).  grid (row chunks, 64-column blocks): thread (row phase rq, column c) owns private f64 sums for every
-// cluster in LDS ([4][K][64]: no atomics, fixed order), the four phases are added, one partial row block per workgroup; a second kernel adds the chunks in order.
+// cluster in LDS ([4][KB][64]: no atomics, fixed order), the four phases are added, one partial row block per workgroup; a second kernel adds the chunks in order.
+// One launch takes the KB <= SEG_KB clusters k0 .. k0 + KB - 1 of the K (the LDS holds 4 * 64 * 64 doubles = 128 KB); a row of another cluster adds nothing.
 constexpr int SEG_CHUNKS = 64;
-__global__ __launch_bounds__(256) void segment_sum_kernel(const double* v, long ldv, const long long* lab, int N, int D, int K, double* part) {
-    extern __shared__ double seg_acc[];                       // [4][K][64]
+constexpr int SEG_KB = 64;
+__global__ __launch_bounds__(256) void segment_sum_kernel(const double* v, long ldv, const long long* lab, int N, int D, int K, int k0, int KB, double* part) {
+    extern __shared__ double seg_acc[];                       // [4][KB][64]
     const int tid = threadIdx.x, c = tid & 63, rq = tid >> 6;
     const int col = blockIdx.y * 64 + c;
-    for (int i = tid; i < 4 * K * 64; i += 256) seg_acc[i] = 0.0;
+    for (int i = tid; i < 4 * KB * 64; i += 256) seg_acc[i] = 0.0;
     __syncthreads();
     const int per = (N + gridDim.x - 1) / gridDim.x;
     const int r0 = blockIdx.x * per, r1 = min(N, r0 + per);
-    double* mine = seg_acc + (size_t)rq * K * 64 + c;
+    double* mine = seg_acc + (size_t)rq * KB * 64 + c;
     if (col < D)
         for (int r = r0 + rq; r < r1; r += 4) {
-            const int k = (int)lab[r];
-            if (k >= 0 && k < K) mine[k * 64] += v[(size_t)r * ldv + col];
+            const long long kl = lab[r] - k0;                 // (compared as 64-bit: a label beyond int wraps into nothing)
+            if (kl >= 0 && kl < KB) mine[(int)kl * 64] += v[(size_t)r * ldv + col];
         }
     __syncthreads();
-    for (int i = tid; i < K * 64; i += 256) {
+    for (int i = tid; i < KB * 64; i += 256) {
         const int k = i >> 6, cc = i & 63;
         if (blockIdx.y * 64 + cc < D)
-            part[((size_t)blockIdx.x * K + k) * D + blockIdx.y * 64 + cc] = (seg_acc[i] + seg_acc[K * 64 + i]) + (seg_acc[2 * K * 64 + i] + seg_acc[3 * K * 64 + i]);
+            part[((size_t)blockIdx.x * K + k0 + k) * D + blockIdx.y * 64 + cc] = (seg_acc[i] + seg_acc[KB * 64 + i]) + (seg_acc[2 * KB * 64 + i] + seg_acc[3 * KB * 64 + i]);
     }
 }
 __global__ __launch_bounds__(256) void segment_sum_finalize(const double* part, int nch, int n, double* out) {
@@ -200,7 +202,6 @@ int dic_cluster_pairdist(const float* X, const int32_t* seg, int N, int D, int K
                          dic_stream_t stream) {
     DIC_REQUIRE(N > 0 && D > 0 && K > 0, DIC_ERR_INVALID_ARG, "cluster_pairdist: non-positive size");
     DIC_REQUIRE(D % 4 == 0, DIC_ERR_UNSUPPORTED, "cluster_pairdist: D=%d must be a multiple of 4", D);
-    DIC_REQUIRE(K <= 64, DIC_ERR_UNSUPPORTED, "cluster_pairdist: K=%d > 64", K);
     DIC_REQUIRE(X && seg && S, DIC_ERR_INVALID_ARG, "cluster_pairdist: NULL pointer");
     const int grid = (N + PT - 1) / PT;
     hipLaunchKernelGGL(pairdist_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, X, seg, N, D, K, S, Dmin, own_max);
@@ -210,7 +211,6 @@ int dic_cluster_pairdist(const float* X, const int32_t* seg, int N, int D, int K
 int dic_cluster_intra_sums(const float* X, const int32_t* seg, int N, int D, int K, float* S_own, dic_stream_t stream) {
     DIC_REQUIRE(N > 0 && D > 0 && K > 0, DIC_ERR_INVALID_ARG, "cluster_intra_sums: non-positive size");
     DIC_REQUIRE(D % 4 == 0, DIC_ERR_UNSUPPORTED, "cluster_intra_sums: D=%d must be a multiple of 4", D);
-    DIC_REQUIRE(K <= 64, DIC_ERR_UNSUPPORTED, "cluster_intra_sums: K=%d > 64", K);
     DIC_REQUIRE(X && seg && S_own, DIC_ERR_INVALID_ARG, "cluster_intra_sums: NULL pointer");
     const int grid = (N + PT - 1) / PT;
     hipLaunchKernelGGL(pairdist_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)stream, X, seg, N, D, K, S_own, (float*)nullptr, (float*)nullptr);
@@ -222,11 +222,10 @@ size_t dic_segment_sum_workspace(int D, int K) { return (D > 0 && K > 0) ? (size
 int dic_segment_sum_f64(const double* values, long ldv, const int64_t* labels, int N, int D, int K, double* out, void* workspace, size_t workspace_bytes,
                         dic_stream_t stream) {
     DIC_REQUIRE(N > 0 && D > 0 && K > 0 && ldv >= D, DIC_ERR_INVALID_ARG, "segment_sum_f64: N=%d D=%d K=%d ldv=%ld", N, D, K, ldv);
-    DIC_REQUIRE(K <= 64, DIC_ERR_UNSUPPORTED, "segment_sum_f64: K=%d > 64", K);
     DIC_REQUIRE(values && labels && out && workspace, DIC_ERR_INVALID_ARG, "segment_sum_f64: NULL pointer");
     DIC_REQUIRE(workspace_bytes >= dic_segment_sum_workspace(D, K), DIC_ERR_WORKSPACE, "segment_sum_f64: workspace %zu < %zu", workspace_bytes,
                 dic_segment_sum_workspace(D, K));
-    const size_t lds = (size_t)4 * K * 64 * sizeof(double);
+    const size_t lds = (size_t)4 * min(K, SEG_KB) * 64 * sizeof(double);
     static size_t lds_set = 0;
     if (lds > lds_set) {
         hipError_t e = hipFuncSetAttribute((const void*)segment_sum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -234,7 +233,9 @@ int dic_segment_sum_f64(const double* values, long ldv, const int64_t* labels, i
         lds_set = lds;
     }
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(segment_sum_kernel, dim3(SEG_CHUNKS, (D + 63) / 64), dim3(256), lds, st, values, ldv, (const long long*)labels, N, D, K, (double*)workspace);
+    for (int k0 = 0; k0 < K; k0 += SEG_KB)          // blocks of 64 clusters: every (chunk, cluster) row of the workspace is written by exactly one launch
+        hipLaunchKernelGGL(segment_sum_kernel, dim3(SEG_CHUNKS, (D + 63) / 64), dim3(256), lds, st, values, ldv, (const long long*)labels, N, D, K, k0,
+                           min(SEG_KB, K - k0), (double*)workspace);
     hipLaunchKernelGGL(segment_sum_finalize, dim3((K * D + 255) / 256), dim3(256), 0, st, (const double*)workspace, SEG_CHUNKS, K * D, out);
     return check_launch("segment_sum_f64");
 }
